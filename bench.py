@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- the per-pixel voxel trace hot path on MI355X (BASELINE.json metric: Mrays/s primary+bounce).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c5] [--no-cpu] [--reseed] [--no-context]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c5] [--reseed] [--dump-outputs DIR]
+                    [--full [--no-cpu] [--no-context]]
 
 A step = one frame: every rank renders its pixel shard (seed classes, or (x ^ y) % N == rank, the reference's own
 partition, with --partition xor) of the SAME frame through Camera.render -> vrt_render_tile (HIP), then the ranks'
 RGBA8 tiles (as int32 words) are gathered to rank 0 (RCCL) and scattered to image order.  Inputs (scene, pixel
 lists, and -- static seeds being the reference default -- the frame-invariant draw and ray tables) are resident in
 HBM before the timed region; --reseed rebuilds both tables inside every timed frame.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K frames, writes the last timed frame's outputs (--dump-outputs) and prints the
+line.  --full adds what takes work of its own: HIP events around the timed frames' march launches (the roofline), every
+kernel kind timed in up to 5 more frames, the re-seeded context frames, the CPU baseline and, for N > 1, the check
+against the committed single-GPU line.
 
 Default workload = BASELINE config 3 (mods/default scene fixture, 3840x2160, samples 8, 8 bounces): the
 configuration the north star's Mrays/s targets are quoted on; c2 / c5 are selectable.
@@ -46,6 +52,11 @@ CONFIGS = {
                          lod_bounces=0.0)),
 }
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+# --dump-outputs: pixel rows (a fixed seeded sample when the shard has more) and traversed chunks (the first ones in visit
+# order) written; 40 and 24 bytes each, so at most 32 MB in all
+DUMP_PIXELS = 1 << 19
+DUMP_TRAVERSED = 1 << 19
+DUMP_SEED = 20260101
 
 
 def load_default_scene(world=False):
@@ -101,6 +112,30 @@ def b_alg(stats, n_px):
     return (lookup + nbr) + 8 * (resnap + chunk_get) + 32 * hit + 8 * draw + 20 * n_px
 
 
+def dump_outputs(path, r, image, chunk_size):
+    """--dump-outputs: what the last timed frame handed its caller, as .npy files in float32 / float64.  r: rank 0's
+    RenderResult; image: the delivered [H, W, 4] uint8 frame (the gathered one for N > 1).
+      pixels.npy      [k, 2] float32  (x, y) of the rows written: all of rank 0's pixels, or a seeded sample of DUMP_PIXELS
+      rgba_f32.npy    [k, 4] float32  per-pixel sample means of those rows
+      image_rgba8.npy [k, 4] float32  the RGBA8 frame at those pixels
+      stats.npy       [12]   float64  counters (nat.COUNTER_NAMES), rays, re-traced, exhausted, outside the traversed box
+      traversed.npy   [t, 3] float64  visited chunk positions in the reference's order, the first DUMP_TRAVERSED"""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    n = int(r.pixels.shape[0])
+    rows = np.arange(n) if n <= DUMP_PIXELS else \
+        np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_PIXELS, replace=False))
+    px = r.pixels[rows]
+    dev_rows = torch.from_numpy(rows).to(r.rgba_f32.device)
+    img = image.contiguous().view(torch.uint8).reshape(image.shape[0], image.shape[1], 4).cpu().numpy()
+    trav = np.asarray(r.traversed(chunk_size)[:DUMP_TRAVERSED], np.float64).reshape(-1, 3)
+    out = {"pixels": px.astype(np.float32), "rgba_f32": r.rgba_f32[dev_rows].cpu().numpy(),
+           "image_rgba8": img[px[:, 1], px[:, 0]].astype(np.float32),
+           "stats": r._stats_dev.cpu().numpy()[:12].astype(np.float64), "traversed": trav}
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def host_volume(scene, materials):
     """The synthetic volume as the oracle wants it (a dense [x][y][z] id grid), copied back from the device and taken out
     of the packed brick order (vrt.h: blocks [cx][cy][cz] of 8^3 bricks of 4^3 micro-bricks).  The device generator is
@@ -144,7 +179,13 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures that take work of their own: the march roofline (HIP events in the timed "
+                         "frames), per-kernel times, the re-seeded context frames, the CPU baseline and, for N > 1, the "
+                         "check against the committed single-GPU line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed frame's outputs to DIR/<name>.npy (bench.dump_outputs)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--partition", default="seed", choices=["seed", "xor", "tiles"],
                     help="pixel partition across ranks for N > 1 (multigpu.owner_map)")
     ap.add_argument("--reseed", action="store_true",
@@ -156,8 +197,8 @@ def main():
                     help="frames submitted on that many HIP streams in turn: with 2, frame k + 1 starts while frame k's "
                          "last waves drain (throughput mode; the per-kernel durations then overlap)")
     ap.add_argument("--no-context", action="store_true",
-                    help="skip the re-seeded context frames after the timed region (profiling runs: every launch a "
-                         "profiler sees is then a warm-up or a timed frame)")
+                    help="with --full: skip the re-seeded context frames after the timed region (profiling runs: every "
+                         "launch a profiler sees is then a warm-up, a timed frame or a per-kernel frame)")
     ap.add_argument("--no-traversed", action="store_true", help="do not record traversed chunks")
     ap.add_argument("--world-flow", action="store_true",
                     help="default scene only: keep the whole world resident (Camera.set_world_scene) and let every frame's "
@@ -165,6 +206,8 @@ def main():
                          "own flow (Window.chunk_update, init.py:441-452) -- instead of rendering the pre-selected fixture; "
                          "the frame must come out identical")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -264,10 +307,10 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    # HIP events around the march launches only (the roofline's kernel): an event pair costs a frame ~12 us, and the three
-    # pairs of a config-2 frame (march, re-trace tiers, resolve) were 6 % of it.  The other kernels are timed in frames of
-    # their own after the timed region (below).  VRT_BENCH_EVENTS=0: none at all (the roofline is then empty).
-    if os.environ.get("VRT_BENCH_EVENTS", "1") != "0":
+    # --full: HIP events around the march launches only (the roofline's kernel): an event pair costs a frame ~12 us, and
+    # the three pairs of a config-2 frame (march, re-trace tiers, resolve) were 6 % of it.  The other kernels are timed in
+    # frames of their own after the timed region (below).  VRT_BENCH_EVENTS=0: none at all (the roofline is then empty).
+    if args.full and os.environ.get("VRT_BENCH_EVENTS", "1") != "0":
         L.vrt_profile_begin_kinds(1 << 1)
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -278,30 +321,38 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    ms = (C.c_double * nat.NPROF)()
-    launches = (C.c_int64 * nat.NPROF)()
-    L.vrt_profile_end(ms, launches)
-    # every kernel kind, in up to 5 more frames of the same kind outside the timed region
-    other_frames = min(args.steps, 5)
-    ms_all = (C.c_double * nat.NPROF)()
-    launches_all = (C.c_int64 * nat.NPROF)()
-    L.vrt_profile_begin()
-    for _ in range(other_frames):
-        step()
-    drain()
-    torch.cuda.synchronize()
-    L.vrt_profile_end(ms_all, launches_all)
+    if args.full:
+        ms = (C.c_double * nat.NPROF)()
+        launches = (C.c_int64 * nat.NPROF)()
+        L.vrt_profile_end(ms, launches)
 
-    stats = last["r"]._stats_dev.cpu().numpy()
+    # the last timed frame (a gathered frame lives in TileGather's buffer until the next gather)
+    r_last = last["r"]
+    frame = last.get("image") if world > 1 else r_last.image_u8
+    stats = r_last._stats_dev.cpu().numpy()
     # SHA-256 of the finished RGBA8 frame (rank 0): identical for every N and partition, or the run is wrong
     import hashlib
-    frame = last.get("image") if world > 1 else last["r"].image_u8
     image_sha = hashlib.sha256(frame.contiguous().cpu().numpy().tobytes()).hexdigest() if frame is not None else None
     if stats[nat.S_RNG_EXHAUSTED]:
         raise SystemExit("invalid run: %d rays exhausted the random-draw tables" % stats[nat.S_RNG_EXHAUSTED])
     if stats[nat.S_TRAV_OUTSIDE] or stats[nat.S_STALLED]:
         raise SystemExit("invalid run: march reported internal errors (outside the traversed box, stalled waves) %r"
                          % stats[[nat.S_TRAV_OUTSIDE, nat.S_STALLED]].tolist())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r_last, frame, int(st.chunk_size))
+
+    if args.full:
+        # every kernel kind, in up to 5 more frames of the same kind outside the timed region
+        other_frames = min(args.steps, 5)
+        ms_all = (C.c_double * nat.NPROF)()
+        launches_all = (C.c_int64 * nat.NPROF)()
+        L.vrt_profile_begin()
+        for _ in range(other_frames):
+            step()
+        drain()
+        torch.cuda.synchronize()
+        L.vrt_profile_end(ms_all, launches_all)
+
     # rays = primary + bounce (shader invocations after which the march continued), SURVEY.md 8d
     local = np.array([int(stats[8]), int(stats[4]) - int(stats[7]), dt] + [int(v) for v in stats[:8]], np.float64)
     if world > 1:
@@ -319,27 +370,6 @@ def main():
     per_step = dt / args.steps
     value = (primary + bounce) / per_step / 1e6
 
-    # roofline of the dominant kernel (march_kernel) on rank 0: algorithmic bytes per launch / mean launch time
-    n_march = int(launches[1]) or 1
-    march_ms = ms[1] / n_march
-    balg_frame = b_alg(stats, len(pixels))
-    balg_launch = balg_frame * args.steps / n_march
-    achieved = balg_launch / (march_ms * 1e-3) / 1e9 if march_ms > 0 else 0.0
-    # HBM traffic of one march launch from the rocprofv3 counters of a SEPARATE run of this command (profiles/
-    # pmc_<config>.json, tools/save_profiles.py): not measured in this process
-    traffic = traffic_hi = None
-    pmc_path = os.path.join(ROOT, "profiles", "pmc_%s.json" % args.config)
-    if os.path.exists(pmc_path) and not args.reseed:
-        pmc = json.load(open(pmc_path))
-        traffic, traffic_hi = pmc.get("hbm_bytes_per_march_launch"), pmc.get("hbm_bytes_per_march_launch_upper")
-    # kernel variant of the frame march: resolution mode (0: all chunks at resolution 1, 1: <= 2, 2: any) and speculation
-    # depth (8 steps for modes 0 and 1 and for voxel data far beyond the caches, else 4: march_deep() in vrt_kernels.hip)
-    sc_ = cam._ensure_scene()
-    deep_env = os.environ.get("VRT_SPEC_DEEP")
-    res_mode_ = {1: 0, 2: 1}.get(int(cam._c_scene(sc_).max_resolution), 2)   # (what vrt_render_tile was told)
-    deep = (int(deep_env) != 0) if deep_env is not None else (res_mode_ != 2 or sc_.n_slots * int(st.chunk_size) ** 3 > (512 << 20))
-    spec_depth = 8 if deep else 4
-    res_mode = res_mode_
     out = {
         "metric": "Mrays/s (primary+bounce)", "value": round(value, 3), "unit": "Mrays/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(per_step * 1e3, 4),
@@ -357,25 +387,47 @@ def main():
                    "rng_retraced_rays": int(stats[nat.S_RNG_RETRACED]),
                    "rng_table": "re-seeded and ray table regenerated in every timed frame (--reseed)" if args.reseed else
                                 "static seeds: draw table + ray table built once before the timed region, reused"},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic,
-                     "traffic_source": "profiles/pmc_%s.json: rocprofv3 FETCH_SIZE x 1 (calibrated for this kernel's 1/8-byte "
-                                       "gathers, profiles/r02_fetch_size_calibration.json) + WRITE_SIZE, separate run" % args.config
-                     if traffic else None,
-                     "kernel": ("march_pool_kernel<%d,%d>" if stats[nat.S_POOL_GROUPS] else "march_kernel<%d,%d,false,false,0>")
-                               % (spec_depth, res_mode), "launches": n_march,
-                     "avg_launch_ms": round(march_ms, 4), "alg_bytes_per_launch": int(balg_launch),
-                     # counter bytes over this run's launch time; the upper bound doubles FETCH_SIZE (the guide's factor
-                     # for wide streaming reads, which this kernel's ray-table and draw reads partly are)
-                     "counter_hbm_GBps": [round(t / (march_ms * 1e-3) / 1e9, 1) if t and march_ms > 0 else None
-                                          for t in (traffic, traffic_hi)],
-                     "alg_bytes_per_primary_ray": round(balg_frame / max(1, int(stats[8])), 2)},
-        # march: HIP events inside the timed region; the others: the same frames again after it, every kernel bracketed
-        "kernel_ms_per_step": {nat.PROF_NAMES[k]: round(ms[k] / args.steps if k == 1 else ms_all[k] / other_frames, 4)
-                               for k in range(len(nat.PROF_NAMES))},
     }
+    if args.full:
+        # roofline of the dominant kernel (march_kernel) on rank 0: algorithmic bytes per launch / mean launch time
+        n_march = int(launches[1]) or 1
+        march_ms = ms[1] / n_march
+        balg_frame = b_alg(stats, len(pixels))
+        balg_launch = balg_frame * args.steps / n_march
+        achieved = balg_launch / (march_ms * 1e-3) / 1e9 if march_ms > 0 else 0.0
+        # HBM traffic of one march launch from the rocprofv3 counters of a SEPARATE run of this command (profiles/
+        # pmc_<config>.json, tools/save_profiles.py): not measured in this process
+        traffic = traffic_hi = None
+        pmc_path = os.path.join(ROOT, "profiles", "pmc_%s.json" % args.config)
+        if os.path.exists(pmc_path) and not args.reseed:
+            pmc = json.load(open(pmc_path))
+            traffic, traffic_hi = pmc.get("hbm_bytes_per_march_launch"), pmc.get("hbm_bytes_per_march_launch_upper")
+        # kernel variant of the frame march: resolution mode (0: all chunks at resolution 1, 1: <= 2, 2: any) and speculation
+        # depth (8 steps for modes 0 and 1 and for voxel data far beyond the caches, else 4: march_deep() in vrt_kernels.hip)
+        sc_ = cam._ensure_scene()
+        deep_env = os.environ.get("VRT_SPEC_DEEP")
+        res_mode_ = {1: 0, 2: 1}.get(int(cam._c_scene(sc_).max_resolution), 2)   # (what vrt_render_tile was told)
+        deep = (int(deep_env) != 0) if deep_env is not None else (res_mode_ != 2 or sc_.n_slots * int(st.chunk_size) ** 3 > (512 << 20))
+        spec_depth = 8 if deep else 4
+        res_mode = res_mode_
+        out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic,
+                           "traffic_source": "profiles/pmc_%s.json: rocprofv3 FETCH_SIZE x 1 (calibrated for this kernel's "
+                                             "1/8-byte gathers, profiles/r02_fetch_size_calibration.json) + WRITE_SIZE, "
+                                             "separate run" % args.config if traffic else None,
+                           "kernel": ("march_pool_kernel<%d,%d>" if stats[nat.S_POOL_GROUPS] else
+                                      "march_kernel<%d,%d,false,false,0>") % (spec_depth, res_mode), "launches": n_march,
+                           "avg_launch_ms": round(march_ms, 4), "alg_bytes_per_launch": int(balg_launch),
+                           # counter bytes over this run's launch time; the upper bound doubles FETCH_SIZE (the guide's
+                           # factor for wide streaming reads, which this kernel's ray-table and draw reads partly are)
+                           "counter_hbm_GBps": [round(t / (march_ms * 1e-3) / 1e9, 1) if t and march_ms > 0 else None
+                                                for t in (traffic, traffic_hi)],
+                           "alg_bytes_per_primary_ray": round(balg_frame / max(1, int(stats[8])), 2)}
+        # march: HIP events inside the timed region; the others: the same frames again after it, every kernel bracketed
+        out["kernel_ms_per_step"] = {nat.PROF_NAMES[k]: round(ms[k] / args.steps if k == 1 else ms_all[k] / other_frames, 4)
+                                     for k in range(len(nat.PROF_NAMES))}
     exit_code = 0
-    if world > 1:
+    if args.full and world > 1:
         # self-check of a multi-GPU run: the gathered frame and the whole-job ray counts must be those of the committed
         # single-GPU line of this configuration (the same frame: static seeds, the same scene and camera)
         ref = single_gpu_reference(args.config)
@@ -391,7 +443,7 @@ def main():
                                            "value": ref[2]["value"]}
             if not same:
                 exit_code = 3
-    if world == 1 and not args.reseed and st.static and not args.no_context:
+    if args.full and world == 1 and not args.reseed and st.static and not args.no_context:
         # context, outside the timed region above: the same K frames with both tables rebuilt in every frame
         cam.cache_draws = False
         step()
@@ -404,7 +456,7 @@ def main():
         cam.cache_draws = True
         out["reseeded_every_frame"] = {"ms_per_step": round(per2 * 1e3, 4),
                                        "value": round((primary + bounce) / per2 / 1e6, 3), "unit": "Mrays/s"}
-    if world == 1 and not args.no_cpu:
+    if args.full and world == 1 and not args.no_cpu:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib as ol
         st_dict = ol.make_settings(width=st.width, height=st.height, samples=st.samples,

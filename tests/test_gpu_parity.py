@@ -1138,16 +1138,17 @@ def test_cached_tables_give_identical_frames(frame_march):
 
 @pytest.mark.one_march
 @pytest.mark.gpu
-def test_bench_two_ranks_render_the_single_gpu_frame():
+def test_bench_two_ranks_render_the_single_gpu_frame(tmp_path):
     """bench.py end to end: one rank, and two ranks launched exactly as the driver does (torch.distributed.run; gloo
     stands in for RCCL because this box has one GPU, both ranks share it) with either pixel partition.  The gathered
-    RGBA8 frame must be bit-identical (same SHA-256) and the whole-job ray counts equal."""
+    RGBA8 frame must be bit-identical (same SHA-256) and the whole-job ray counts equal.  A plain one-rank run (no
+    --full) renders the same frame, and its --dump-outputs files are those of the --full run."""
     import socket
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-    def run(n, extra):
+    def run(n, extra, full=True):
         env = dict(os.environ)
         env["VRT_BENCH_BACKEND"] = "gloo"
         cmd = [sys.executable]
@@ -1158,18 +1159,32 @@ def test_bench_two_ranks_render_the_single_gpu_frame():
             s.close()
             cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
                     "--master-port", str(port)]
-        cmd += [os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--config", "c2",
-                "--no-cpu"] + extra
+        cmd += [os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--config", "c2"] + \
+            (["--full", "--no-cpu"] if full else []) + extra
         out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
         assert out.returncode == 0, out.stderr[-3000:]
         lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
         assert len(lines) == 1, out.stdout[-2000:]
         return json.loads(lines[0])
 
-    one = run(1, [])
+    one = run(1, ["--dump-outputs", str(tmp_path / "full")])
     assert one["n_gpus"] == 1 and one["config"]["primary_rays"] == 1920 * 1080
     for key in ("roofline", "kernel_ms_per_step", "reseeded_every_frame"):
         assert key in one
+    plain = run(1, ["--dump-outputs", str(tmp_path / "plain")], full=False)
+    for key in ("roofline", "kernel_ms_per_step", "reseeded_every_frame", "cpu_baseline"):
+        assert key not in plain
+    assert plain["steps"] == 2 and plain["ms_per_step"] > 0
+    for key in ("image_sha256", "primary_rays", "bounce_rays"):
+        assert plain["config"][key] == one["config"][key]
+    names = ("pixels", "rgba_f32", "image_rgba8", "stats", "traversed")
+    assert sorted(os.listdir(tmp_path / "plain")) == sorted(n + ".npy" for n in names)
+    for name in names:
+        a, b = np.load(tmp_path / "plain" / (name + ".npy")), np.load(tmp_path / "full" / (name + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and np.array_equal(a, b), name
+    px, st = np.load(tmp_path / "plain" / "pixels.npy"), np.load(tmp_path / "plain" / "stats.npy")
+    assert len(px) == 1 << 19 and len(np.unique(px[:, 1] * 1920 + px[:, 0])) == len(px)
+    assert st[8] == one["config"]["primary_rays"] and st[4] - st[7] == one["config"]["bounce_rays"]
     for extra in ([], ["--partition", "xor"]):
         two = run(2, extra)
         assert two["n_gpus"] == 2 and two["scaling"] == "strong"
@@ -1201,7 +1216,8 @@ def test_bench_two_ranks_over_rccl():
     env.pop("VRT_BENCH_BACKEND", None)
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu"]
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
+           "--no-cpu"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])

@@ -260,12 +260,9 @@ def test_camera_without_gpu_fails_loudly():
 
 
 def test_load_settings_reads_the_reference_default_config():
-    """Row S: parsing the reference's own mods/default/config.cfg (when the checkout is present) gives the render
+    """Row S: parsing the reference's own mods/default/config.cfg (a copy in tests/golden/mod_default) gives the render
     settings the golden fixtures were generated with (reference data.py:15-68)."""
-    cfg = "/root/reference/mods/default/config.cfg"
-    if not os.path.exists(cfg):
-        pytest.skip("reference checkout not present")
-    s = load_settings(cfg, threads=1)
+    s = load_settings(os.path.join(ol.GOLDEN, "mod_default", "config.cfg"), threads=1)
     g = ol.load_render("g64")["settings"]
     for k in ("width", "height", "samples", "static", "shutter", "falloff", "chunk_size", "chunk_lod", "fov", "dof",
               "dist_min", "dist_max", "max_light", "max_bounces", "lod_bounces", "lod_samples", "lod_random", "lod_edge",

@@ -67,15 +67,14 @@ def test_world_build_matches_reference():
                 assert got == (0 if m is None else 1 + w.materials.index(m))
 
 
-REF_VOXELS = "/root/reference/mods/default/voxels"
+REF_VOXELS = os.path.join(ol.GOLDEN, "mod_default", "voxels")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_VOXELS), reason="the reference's asset files only exist in the build container")
 def test_default_mod_assets_build_the_fixture_scene():
-    """The reference's own Goxel exports (castle 209 k voxels, material cube, player) through Sprite.load / Object /
-    build_world, placed as mods/default/init.py:175-214 places them, give exactly the voxel grid the real reference
-    produced for the scene fixture (tests/golden/scene_default.npz) -- including the mirrored-X off-by-one that drops
-    the castle's x = 0 column.  Reads the asset files in place; nothing of them is copied into the repository."""
+    """The reference's own Goxel exports (castle 209 k voxels, material cube, player; copies of mods/default/voxels in
+    tests/golden/mod_default/voxels) through Sprite.load / Object / build_world, placed as mods/default/init.py:175-214
+    places them, give exactly the voxel grid the real reference produced for the scene fixture
+    (tests/golden/scene_default.npz) -- including the mirrored-X off-by-one that drops the castle's x = 0 column."""
     sc = ol.default_scene()
     names = list(sc.names)
     mat = {n: Material(function=material, albedo=rgb(*[int(v) for v in row[:3]]), roughness=row[3], absorption=row[4],

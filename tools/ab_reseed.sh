@@ -3,7 +3,7 @@
 # with raygen_tile_kernel writing a ray table (VRT_FUSE_RAYGEN=0), alternating; one line per run
 out=$1; mkdir -p $out
 for f in 1 0 1 0; do
-  VRT_FUSE_RAYGEN=$f python bench.py --reseed --no-cpu --steps 10 ${AB_FLAGS} > $out/reseed_f$f.json 2> $out/reseed_f$f.err || exit 1
+  VRT_FUSE_RAYGEN=$f python bench.py --full --reseed --no-cpu --steps 10 ${AB_FLAGS} > $out/reseed_f$f.json 2> $out/reseed_f$f.err || exit 1
   python - $out/reseed_f$f.json $f <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

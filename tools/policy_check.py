@@ -16,7 +16,8 @@ print("|---|---|---|---|---|---|---|")
 for cfg in sys.argv[1:] or ["x1", "x2", "x3"]:
     for name, extra in RUNS:
         env = dict(os.environ, **extra)
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--steps", "10", "--warmup", "3",
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", cfg, "--steps", "10",
+                              "--warmup", "3",
                               "--no-cpu", "--no-context"], env=env, capture_output=True, text=True, timeout=600)
         if out.returncode != 0:
             print("|", cfg, "| |", name, "| FAILED |", out.stderr[-200:].replace("\n", " "), "| | |")

@@ -14,25 +14,25 @@ cd /tmp; export TMPDIR=/tmp
 if [ $PART != 2 ]; then
 # --no-context: every march launch the profiler sees is the warm-up frame or one of the timed frames
 for cfg in c3 c5 c2; do
-  rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch_$cfg -- python3 $R/bench.py --config $cfg --steps 3 --warmup 1 --no-cpu --no-context > /dev/null
-  rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write_$cfg -- python3 $R/bench.py --config $cfg --steps 3 --warmup 1 --no-cpu --no-context > /dev/null
+  rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch_$cfg -- python3 $R/bench.py --full --config $cfg --steps 3 --warmup 1 --no-cpu --no-context > /dev/null
+  rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write_$cfg -- python3 $R/bench.py --full --config $cfg --steps 3 --warmup 1 --no-cpu --no-context > /dev/null
 done
 python3 $R/tools/save_profiles.py $TAG --pmc-only
-python3 $R/bench.py --config c3 > $O/bench_c3.json
-python3 $R/bench.py --config c2 --no-cpu > $O/bench_c2.json
-python3 $R/bench.py --config c5 --steps 5 --warmup 1 > $O/bench_c5.json
-python3 $R/bench.py --config c3 --no-cpu --reseed > $O/bench_c3_reseed.json
-python3 $R/bench.py --config c2 --no-cpu --reseed > $O/bench_c2_reseed.json
+python3 $R/bench.py --full --config c3 > $O/bench_c3.json
+python3 $R/bench.py --full --config c2 --no-cpu > $O/bench_c2.json
+python3 $R/bench.py --full --config c5 --steps 5 --warmup 1 > $O/bench_c5.json
+python3 $R/bench.py --full --config c3 --no-cpu --reseed > $O/bench_c3_reseed.json
+python3 $R/bench.py --full --config c2 --no-cpu --reseed > $O/bench_c2_reseed.json
 # the uncached frame with a ray table written and read back (VRT_FUSE_RAYGEN=0: raygen_tile_kernel), beside the default
-VRT_FUSE_RAYGEN=0 python3 $R/bench.py --config c3 --no-cpu --reseed > $O/bench_c3_reseed_table.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c3_reseed -- python3 $R/bench.py --config c3 --steps 10 --warmup 1 --no-cpu --no-context --reseed > $O/prof_c3_reseed_bench.json
+VRT_FUSE_RAYGEN=0 python3 $R/bench.py --full --config c3 --no-cpu --reseed > $O/bench_c3_reseed_table.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c3_reseed -- python3 $R/bench.py --full --config c3 --steps 10 --warmup 1 --no-cpu --no-context --reseed > $O/prof_c3_reseed_bench.json
 for cfg in c3 c5 c2; do
   steps=20; [ $cfg = c5 ] && steps=5
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$cfg -- python3 $R/bench.py --config $cfg --steps $steps --warmup 1 --no-cpu --no-context > $O/prof_${cfg}_bench.json
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$cfg -- python3 $R/bench.py --full --config $cfg --steps $steps --warmup 1 --no-cpu --no-context > $O/prof_${cfg}_bench.json
 done
 # the reference's own flow: world resident, chunks + LOD selected on the device every frame (bench.py --world-flow)
-python3 $R/bench.py --config c3 --no-cpu --world-flow > $O/bench_c3_world.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c3_world -- python3 $R/bench.py --config c3 --steps 20 --warmup 1 --no-cpu --no-context --world-flow > $O/prof_c3_world_bench.json
+python3 $R/bench.py --full --config c3 --no-cpu --world-flow > $O/bench_c3_world.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c3_world -- python3 $R/bench.py --full --config c3 --steps 20 --warmup 1 --no-cpu --no-context --world-flow > $O/prof_c3_world_bench.json
 echo part 1 done
 fi
 [ $PART = 1 ] && exit 0
@@ -41,18 +41,18 @@ fi
 if [ $PART = 2 ]; then
   for cfg in c3 c5; do
     steps=20; [ $cfg = c5 ] && steps=5
-    rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof2_$cfg -- python3 $R/bench.py --config $cfg --steps $steps --warmup 1 --no-cpu --no-context > $O/prof2_${cfg}_bench.json
+    rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof2_$cfg -- python3 $R/bench.py --full --config $cfg --steps $steps --warmup 1 --no-cpu --no-context > $O/prof2_${cfg}_bench.json
   done
 fi
 # the one-ray-per-lane march on the same box (VRT_POOL=0), for the pool's variant table
 for cfg in c3 c5; do
   steps=20; [ $cfg = c5 ] && steps=5
-  VRT_POOL=0 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${cfg}_lanes -- python3 $R/bench.py --config $cfg --steps $steps --warmup 1 --no-cpu --no-context > $O/prof_${cfg}_lanes_bench.json
+  VRT_POOL=0 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${cfg}_lanes -- python3 $R/bench.py --full --config $cfg --steps $steps --warmup 1 --no-cpu --no-context > $O/prof_${cfg}_lanes_bench.json
 done
 # the measured variant whose look-ahead crosses chunk borders (VRT_WADDR=1, march_step_w): config 3 with the ray pool,
 # config 5 with one ray per lane (its world-axis tables and the ray pools do not fit a workgroup's LDS together)
-VRT_WADDR=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c3_ahead -- python3 $R/bench.py --config c3 --steps 20 --warmup 1 --no-cpu --no-context > $O/prof_c3_ahead_bench.json
-VRT_WADDR=1 VRT_POOL=0 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c5_lanes_ahead -- python3 $R/bench.py --config c5 --steps 5 --warmup 1 --no-cpu --no-context > $O/prof_c5_lanes_ahead_bench.json
+VRT_WADDR=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c3_ahead -- python3 $R/bench.py --full --config c3 --steps 20 --warmup 1 --no-cpu --no-context > $O/prof_c3_ahead_bench.json
+VRT_WADDR=1 VRT_POOL=0 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c5_lanes_ahead -- python3 $R/bench.py --full --config c5 --steps 5 --warmup 1 --no-cpu --no-context > $O/prof_c5_lanes_ahead_bench.json
 # SQ counters of both configurations (three passes each), L2 counters, the instrumented build's loop statistics, 1/N shares
 cd $R
 for cfg in c3 c5; do bash tools/pmc_run.sh $cfg "--config $cfg"; done

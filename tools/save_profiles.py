@@ -46,7 +46,7 @@ for cfg in ("c3", "c5", "c2"):
             continue
         f, w = s[k[0]]["FETCH_SIZE"], s[k[0]]["WRITE_SIZE"]
         out = {"config": cfg, "tag": tag,
-               "command": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE --output-format csv -- python3 bench.py --config %s "
+               "command": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE --output-format csv -- python3 bench.py --full --config %s "
                           "--steps 3 --warmup 1 --no-cpu (separate passes); first launch of each kernel left out" % cfg,
                "kernel": k[0].replace("void ", ""), "launches": f["n"],
                "march_fetch_KB_per_launch": f["mean"], "march_write_KB_per_launch": w["mean"],

@@ -14,7 +14,7 @@ for setting in sys.argv[2:]:
     for kv in setting.split():
         k, v = kv.split("=")
         env[k] = v
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", cfg, "--no-cpu", "--steps", steps,
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--config", cfg, "--no-cpu", "--steps", steps,
                           "--warmup", "2"], env=env, capture_output=True, text=True)
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]
     if not line:

@@ -10,7 +10,7 @@ for combo in sys.argv[2:]:
     for n, v in zip(names, combo.split(",")):
         if v != "-":
             env[n] = v
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--steps", steps, "--warmup", warm,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", cfg, "--steps", steps, "--warmup", warm,
                           "--no-cpu", "--no-context"], env=env, capture_output=True, text=True, timeout=600)
     if out.returncode != 0:
         print(combo, "FAILED", out.stderr[-300:])
