@@ -194,8 +194,9 @@ def _orc_settings(s, seed_nonce=0, has_background=True):
 
 
 def render(scene, settings, cam_pos, cam_rot, cam_lens, pixels, libm=LIBM_GLIBC, threads=1, want_rays=True,
-           want_traversed=True, seed_nonce=0, has_background=True):
-    """Run the oracle on `pixels` ([n,2] int32 of (x, y)).  Returns a dict of numpy arrays."""
+           want_traversed=True, seed_nonce=0, has_background=True, trav_cap=1 << 16):
+    """Run the oracle on `pixels` ([n,2] int32 of (x, y)).  Returns a dict of numpy arrays.  trav_cap: room of the traversed
+    list in chunks (a frame that visits more raises)."""
     L = lib()
     st = _orc_settings(settings, seed_nonce, has_background)
     sc = OrcScene()
@@ -218,7 +219,7 @@ def render(scene, settings, cam_pos, cam_rot, cam_lens, pixels, libm=LIBM_GLIBC,
     rays = np.zeros(cap, RAY_DTYPE) if want_rays else None
     n_rays = C.c_int64(0)
     counters = np.zeros(8, np.int64)
-    tcap = 1 << 16
+    tcap = int(trav_cap)
     trav = np.zeros((tcap, 3), np.int64) if want_traversed else None
     n_trav = C.c_int64(0)
     rc = L.orc_render(C.byref(sc), C.byref(st), C.byref(cam), pixels.ctypes.data, n_px, libm, threads,

@@ -6,10 +6,8 @@ import os
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# the newest set that tools/save_profiles.py committed
-TAG = max((os.path.basename(p).split("_bench_")[0] for p in glob.glob(os.path.join(ROOT, "profiles", "r*_v*_bench_c3.json"))),
-          key=lambda t: [int(v) for v in t.replace("r", "").replace("v", "").split("_")])
+from profile_util import ROOT, TAG, committed_kernel_stats, frame_march_rows
+
 LINES = sorted(glob.glob(os.path.join(ROOT, "profiles", TAG + "_bench_*.json")))
 
 
@@ -55,20 +53,10 @@ def test_headline_line_has_a_cpu_baseline():
 def test_rocprof_average_agrees_with_the_bench_line(cfg):
     """`rocprofv3 --kernel-trace --stats` of the same bench command: the dominant kernel's average duration agrees
     with the duration bench.py measured with HIP events (both committed by tools/save_profiles.py)."""
-    import csv
     d = json.loads(open(os.path.join(ROOT, "profiles", "%s_prof_%s_bench.json" % (TAG, cfg))).read())
-    rows = list(csv.DictReader(open(os.path.join(ROOT, "profiles", "%s_%s_kernel_stats.csv" % (TAG, cfg)))))
-    def frame_march(name):   # march_pool_kernel, or march_kernel<SPEC, RES, RECORD = false, LIST = false, ...>
-        if name.startswith("void march_pool_kernel<"):
-            return True
-        if not name.startswith("void march_kernel<"):
-            return False
-        args = [a.strip() for a in name[len("void march_kernel<"):].split(">")[0].split(",")]
-        return args[2] == "false" and args[3] == "false"
-    march = [r for r in rows if frame_march(r["Name"])]
     # (config 5 runs two instances of the frame march: the frames that record `traversed` -- every timed one -- compare a
     # re-snap's key behind the voxel reads, the frames in which bench.py builds its tables record nothing)
-    march.sort(key=lambda r: -float(r["TotalDurationNs"]))
+    march = frame_march_rows(committed_kernel_stats(cfg))     # (profile_util.frame_march: the name filter)
     assert d["roofline"]["kernel"].split("<")[0] == march[0]["Name"].replace("void ", "").split("<")[0]
     assert len(march) <= 2 and int(march[0]["Calls"]) >= d["steps"]
     # rocprof also saw the untimed first frame (cold caches, tables being built: the one slowest call), which is left out;

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
-from gpu_util import camera_for, settings_store
+from gpu_util import bitmap_window, camera_for, settings_store, sparse_scene, window_split
 
 pytestmark = pytest.mark.gpu
 
@@ -53,11 +53,15 @@ def gpu_render(name, **kw):
     return g, st, sc, cam, r
 
 
-def check_frame_march(cam, o, cs, which, lookahead=None, **kw):
+def check_frame_march(cam, o, cs, which, lookahead=None, window=None, **kw):
     """The same frame WITHOUT ray records: `want_rays` selects the recording march_kernel whatever VRT_POOL says, so this is
     the render that runs the frame kernel the fixture names -- march_pool_kernel under "pool" (asserted: its workgroups
     count themselves in stats[12]), march_kernel under "lanes".  Per-sample colours, fp32 means, event counters and the
-    traversed list against the oracle."""
+    traversed list against the oracle.
+    window: what the VRT_TRAV_WINDOW=2 leg below must have been able to do -- True: the traversed box is one that gets the
+    32^3-cell bitmap window (every side of 32 cells and more) AND the oracle's list has chunks both inside that window
+    (the settled bit) and outside it (the key read at every visit); False: the box is too small for a window.  The result
+    says which it was (`window`: the window's lowest cell, or None)."""
     r = cam.render(0, want_ray_rgba=True, **kw)
     groups = int(r.stats[12]) & 0xffffffff     # (bits 32+: the workgroups that took their rays as tiles)
     assert (groups > 0) if which.startswith("pool") else (groups == 0), (which, groups)
@@ -94,6 +98,14 @@ def check_frame_march(cam, o, cs, which, lookahead=None, **kw):
         del os.environ["VRT_TRAV_WINDOW"], os.environ["VRT_DEFER_VISIT"]
     assert np.array_equal(r4.ray_rgba.cpu().numpy(), r.ray_rgba.cpu().numpy()) and (r4.stats[:9] == r.stats[:9]).all()
     assert np.array_equal(r4.traversed_keys.cpu().numpy(), r.traversed_keys.cpu().numpy())
+    # (could that leg use the window at all?  From the box it was handed, not from anything the library reports)
+    assert r4.trav_origin == r.trav_origin and r4.trav_dims == r.trav_dims
+    r.window = bitmap_window([float(cam.pos.x), float(cam.pos.y), float(cam.pos.z)], cs, r4.trav_origin, r4.trav_dims)
+    if window is not None:
+        assert (r.window is not None) == bool(window), (r4.trav_dims, r.window)
+    if window:
+        inside = window_split(o["traversed"], cs, r4.trav_origin, r.window)
+        assert inside.any() and (~inside).any(), (int(inside.sum()), int((~inside).sum()))
     # ... and once without the cached ray table (Camera.cache_draws = False): the frame's draws are seeded anew and the march
     # works out every ray's lens quaternion and life itself instead of reading raygen_tile_kernel's records -- asserted where
     # the library has such a march (stats[15]: not for resolutions > 2, the look-ahead variant or one record per pixel)
@@ -216,6 +228,8 @@ def test_rays_bit_exact_vs_oracle(name, frame_march):
     trav = np.array(r.traversed(st["chunk_size"]), np.int64).reshape(-1, 3)
     assert np.array_equal(trav, o["traversed"])
     # (the fixture scenes are small boxes at resolutions <= 2: laid out in table order, marched across chunk borders)
+    # (dist_max 192 over 16-cell chunks: 29 cells a side for an unrotated camera -- below the 32 the settled-bitmap window
+    # needs; test_settled_bitmap_window_inside_and_outside has the boxes that get one)
     check_frame_march(cam, o, st["chunk_size"], frame_march, lookahead=frame_march.endswith("-ahead"))
 
 
@@ -790,6 +804,36 @@ def test_axis_aligned_rays_from_integer_and_boundary_cameras(pos, frame_march):
         check_frame_march(cam, o, cs, frame_march)    # the frame march (no ray records)
 
 
+WINDOW_SCENES = {"res2": (1, 2, 139, (1.5, 2.25, -3.5)), "res3": (2, 3, 136, (-2.5, 1.25, 3.5))}   # seed, resolutions, dist_max, camera
+
+
+@pytest.mark.parametrize("case", sorted(WINDOW_SCENES))
+def test_settled_bitmap_window_inside_and_outside(case, frame_march):
+    """The settled bitmap over the 32^3 cells around the camera (VRT_TRAV_WINDOW=2 leg of check_frame_march) on boxes that
+    have one: chunk size 8 and dist_max 139 / 136 give an unrotated camera a box of 39 cells a side, the window covers
+    cells 3..34 of it, and rays that fly out of the small sparse world reach the cells beyond (16 and 17 chunks ahead).
+    Measured with the oracle alone, 48 x 36 pixels, 2 samples: "res2" (resolutions 1..2: the kernels that can compare a
+    key behind the voxel reads) visits 2059 chunks inside the window and 72 outside it -- counted per pixel, 28644 visits
+    inside and 115 outside; "res3" (resolutions 1..3: the generic kernels) 2012 and 47 chunks, 30210 and 68 visits.
+    check_frame_march asserts that both sides are there before it trusts the leg; every ray against the oracle as usual."""
+    seed, res_max, dist_max, pos = WINDOW_SCENES[case]
+    cs = 8
+    sc = sparse_scene(seed, res_max, cs)
+    assert int(sc.res[sc.present != 0].max()) == res_max
+    st = ol.make_settings(width=48, height=36, samples=2, max_bounces=4.0, chunk_size=cs, dist_max=dist_max)
+    q, lens = np.array([0.0, 0.0, 0.0, 1.0]), st["fov"] * np.pi / 8
+    cam = camera_for(sc, settings_store(st), np.array(pos), q, lens)
+    r = cam.render(0, want_rays=True)
+    assert r.trav_dims == [39, 39, 39]
+    o = ol.render(sc, st, np.array(pos), q, lens, r.pixels, libm=ol.LIBM_PORTABLE)
+    got, exp = active(r), o["rays"]
+    for f in ("color", "alpha", "counters", "ntrav", "energy", "step", "life", "bounces", "pos", "vel"):
+        assert np.array_equal(got[f], exp[f]), f
+    assert np.array_equal(np.array(r.traversed(cs), np.int64).reshape(-1, 3), o["traversed"])
+    rf = check_frame_march(cam, o, cs, frame_march, window=True)
+    assert rf.window == [3, 3, 3]
+
+
 # ------------------------------------------------------------------------------------------------- chunk selection
 def test_chunk_update_culling_sequence_vs_reference():
     """Camera.chunk_update (vrt_select_chunks): LOD selection + culling feedback over five consecutive frames of the
@@ -878,7 +922,7 @@ _KNOB_SCRIPT = r"""
 import sys, hashlib, numpy as np
 sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
 import oracle_lib as ol
-from gpu_util import camera_for, settings_store
+from gpu_util import bitmap_window, camera_for, settings_store, sparse_scene, window_split
 sc = ol.default_scene()
 st = ol.make_settings(width=160, height=90, samples=4, max_bounces=8)
 cam = camera_for(sc, settings_store(st), sc.cam_pos, sc.cam_rot, sc.cam_lens)
