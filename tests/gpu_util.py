@@ -1,5 +1,9 @@
 """Helpers shared by the GPU parity tests, smoke() and bench.py: build a python_raytracer_amd.Camera from the
-dense fixture scenes and from oracle-style settings dicts."""
+dense fixture scenes and from oracle-style settings dicts; the frame-march check the GPU test modules share."""
+import os
+
+import numpy as np
+
 from python_raytracer_amd import Camera, PackedScene
 from python_raytracer_amd.data import finalize_settings
 from python_raytracer_amd.lib import store, vec3, quaternion
@@ -61,3 +65,110 @@ def sparse_scene(seed, res_max, chunk_size=8, dims=(6, 6, 6), fill=0.02):
                      [220, 220, 220, 1.0, 2.0, 1.0, 0.0]])
     grid = np.where(rng.random(tuple(dims * cs)) < fill, rng.integers(1, 5, tuple(dims * cs)), 0).astype(np.uint8)
     return ol.Scene(origin, dims, cs, present, res, ol.Scene.camera_grid(grid, origin, dims, cs, present, res), mats)
+
+
+def check_frame_march(cam, o, cs, which, lookahead=None, window=None, **kw):
+    """The same frame WITHOUT ray records: `want_rays` selects the recording march_kernel whatever VRT_POOL says, so this is
+    the render that runs the frame kernel the fixture names -- march_pool_kernel under "pool" (asserted: its workgroups
+    count themselves in stats[12]), march_kernel under "lanes".  Per-sample colours, fp32 means, event counters and the
+    traversed list against the oracle.
+    window: what the VRT_TRAV_WINDOW=2 leg below must have been able to do -- True: the traversed box is one that gets the
+    32^3-cell bitmap window (every side of 32 cells and more) AND the oracle's list has chunks both inside that window
+    (the settled bit) and outside it (the key read at every visit); False: the box is too small for a window.  The result
+    says which it was (`window`: the window's lowest cell, or None)."""
+    r = cam.render(0, want_ray_rgba=True, **kw)
+    groups = int(r.stats[12]) & 0xffffffff     # (bits 32+: the workgroups that took their rays as tiles)
+    assert (groups > 0) if which.startswith("pool") else (groups == 0), (which, groups)
+    if lookahead is not None:   # did the march step look ahead across chunk borders (march_step_w)?
+        assert (int(r.stats[14]) > 0) == bool(lookahead), (lookahead, int(r.stats[14]))
+    assert np.array_equal(r.rgba_f32.cpu().numpy(), o["pix_mean"].astype(np.float32))
+    assert (r.stats[:8] == o["counters"]).all(), (r.stats[:8], o["counters"])
+    assert np.array_equal(np.array(r.traversed(cs), np.int64).reshape(-1, 3), np.asarray(o["traversed"]).reshape(-1, 3))
+    rays = o["rays"]
+    where = {(int(x), int(y)): i for i, (x, y) in enumerate(r.pixels)}
+    slot = np.array([where[(int(x), int(y))] for x, y in zip(rays["x"], rays["y"])], np.int64) * r.max_samples + rays["s"]
+    packed = (rays["color"][:, 0].astype(np.uint32) | (rays["color"][:, 1].astype(np.uint32) << 8) |
+              (rays["color"][:, 2].astype(np.uint32) << 16) | (rays["alpha"].astype(np.uint32) << 24))
+    got = r.ray_rgba.cpu().numpy().view(np.uint32)
+    assert np.array_equal(got[slot], packed)
+    # ... and once more without the settled-cell bitmap (VRT_TRAV_LDS=0, read at every launch): what traversed boxes too large
+    # for one get -- every visit reads its cell's key, and the kernel instances that compare it after the voxel reads run
+    # -- and, where the window's geometry allows (the pool kernel, a power-of-two run of pixels per hand-out that divides the
+    # height), with the rays handed out as square tiles in Morton order from eight heads (VRT_TILED=2: tile_ticket)
+    os.environ["VRT_TRAV_LDS"], os.environ["VRT_DEFER_VISIT"], os.environ["VRT_TILED"] = "0", "2", "2"   # (2: also over scenes that fit the caches)
+    try:
+        r2 = cam.render(0, want_ray_rgba=True, **kw)
+    finally:
+        del os.environ["VRT_TRAV_LDS"], os.environ["VRT_DEFER_VISIT"], os.environ["VRT_TILED"]
+    assert np.array_equal(r2.ray_rgba.cpu().numpy(), r.ray_rgba.cpu().numpy()) and (r2.stats[:9] == r.stats[:9]).all()
+    assert np.array_equal(r2.traversed_keys.cpu().numpy(), r.traversed_keys.cpu().numpy())
+    # ... with the settled bitmap of boxes too large for one of their own: over the 32^3 cells around the camera only
+    # (VRT_TRAV_WINDOW=2 uses it for every box of at least 32^3 cells; smaller boxes render as before)
+    # -- together with the key comparison behind the voxel reads, as scenes beyond the caches run it
+    os.environ["VRT_TRAV_WINDOW"], os.environ["VRT_DEFER_VISIT"] = "2", "2"
+    try:
+        r4 = cam.render(0, want_ray_rgba=True, **kw)
+    finally:
+        del os.environ["VRT_TRAV_WINDOW"], os.environ["VRT_DEFER_VISIT"]
+    assert np.array_equal(r4.ray_rgba.cpu().numpy(), r.ray_rgba.cpu().numpy()) and (r4.stats[:9] == r.stats[:9]).all()
+    assert np.array_equal(r4.traversed_keys.cpu().numpy(), r.traversed_keys.cpu().numpy())
+    # (could that leg use the window at all?  From the box it was handed, not from anything the library reports)
+    assert r4.trav_origin == r.trav_origin and r4.trav_dims == r.trav_dims
+    r.window = bitmap_window([float(cam.pos.x), float(cam.pos.y), float(cam.pos.z)], cs, r4.trav_origin, r4.trav_dims)
+    if window is not None:
+        assert (r.window is not None) == bool(window), (r4.trav_dims, r.window)
+    if window:
+        inside = window_split(o["traversed"], cs, r4.trav_origin, r.window)
+        assert inside.any() and (~inside).any(), (int(inside.sum()), int((~inside).sum()))
+    # ... and once without the cached ray table (Camera.cache_draws = False): the frame's draws are seeded anew and the march
+    # works out every ray's lens quaternion and life itself instead of reading raygen_tile_kernel's records -- asserted where
+    # the library has such a march (stats[15]: not for resolutions > 2, the look-ahead variant or one record per pixel)
+    s = cam._settings()
+    fused = (not which.endswith("-ahead") and 1 <= int(cam._c_scene(cam._ensure_scene()).max_resolution) <= 2 and
+             (float(s.dof) != 0.0 or float(s.lod_random) != 0.0 or float(s.lod_samples) != 0.0))
+    cached, cam.cache_draws = cam.cache_draws, False
+    try:
+        r3 = cam.render(0, want_ray_rgba=True, **kw)
+    finally:
+        cam.cache_draws = cached
+    if fused:
+        assert int(r3.stats[15]) > 0, r3.stats
+    assert np.array_equal(r3.ray_rgba.cpu().numpy(), r.ray_rgba.cpu().numpy()) and (r3.stats[:9] == r.stats[:9]).all()
+    assert np.array_equal(r3.traversed_keys.cpu().numpy(), r.traversed_keys.cpu().numpy())
+    return r
+
+
+def active(r):
+    rays = r.rays
+    return rays[rays["s"] >= 0]
+
+
+def check_tile_plan(dp, st):
+    """A built tile plan (DevicePixels.plan: the static distinct-seed index of include/vrt.h, vrt_plan_build) against a
+    numpy restatement, for every pixel and sample slot of the list: the header's counts, the sorted distinct seeds and
+    the seed index of every slot (0xFFFFFFFF for a slot the pixel's sample count leaves unused).  st: the oracle-style
+    settings dict the plan was built for.  Returns the header words."""
+    import ctypes as C
+    import oracle_lib as ol
+    px = dp.array.astype(np.int64)
+    ost = ol._orc_settings(st)
+    L = ol.lib()
+    ns = np.array([L.orc_pixel_samples(C.byref(ost), int(x), int(y)) for x, y in px], np.int64).reshape(-1)
+    raw = dp.plan.cpu().numpy()
+    hdr = raw[:64].view(np.uint64)
+    smax = max(1, round(st["samples"] * (1 - min(st["lod_edge"], 0.0))))           # vrt_max_samples (init.py:133-134)
+    assert ns.max(initial=1) <= smax
+    used = np.arange(smax)[None, :] < ns[:, None]                                   # [n_px, smax]: the slots that hold a ray
+    seeds = ((1 + px[:, 0]) * (1 + px[:, 1]))[:, None] * (1 + np.arange(smax))[None, :]
+    distinct = np.unique(seeds[used])
+    assert dp.n_distinct == len(distinct)
+    slots = len(px) * smax
+    assert hdr[1] == len(px) and hdr[2] == slots and hdr[3] == len(distinct)
+    seed_list = raw[64:64 + 4 * slots].view(np.uint32)[: len(distinct)]
+    assert np.array_equal(seed_list.astype(np.int64), distinct)                    # sorted, unique
+    off = 64 + ((4 * slots + 255) // 256) * 256
+    idx = raw[off:off + 4 * slots].view(np.uint32).reshape(len(px), smax)
+    assert (idx[~used] == 0xFFFFFFFF).all()
+    assert (idx[used] < len(distinct)).all()
+    assert np.array_equal(seed_list[idx[used]].astype(np.int64), seeds[used])
+    return hdr

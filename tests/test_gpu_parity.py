@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
-from gpu_util import bitmap_window, camera_for, settings_store, sparse_scene, window_split
+from gpu_util import (active, bitmap_window, camera_for, check_frame_march, check_tile_plan, settings_store, sparse_scene,
+                      window_split)
 
 pytestmark = pytest.mark.gpu
 
@@ -51,82 +52,6 @@ def gpu_render(name, **kw):
     cam = camera_for(sc, settings_store(st), g["cam_pos"], g["cam_rot"], g["cam_lens"][0])
     r = cam.render(0, want_rays=True, want_ray_rgba=True, **kw)
     return g, st, sc, cam, r
-
-
-def check_frame_march(cam, o, cs, which, lookahead=None, window=None, **kw):
-    """The same frame WITHOUT ray records: `want_rays` selects the recording march_kernel whatever VRT_POOL says, so this is
-    the render that runs the frame kernel the fixture names -- march_pool_kernel under "pool" (asserted: its workgroups
-    count themselves in stats[12]), march_kernel under "lanes".  Per-sample colours, fp32 means, event counters and the
-    traversed list against the oracle.
-    window: what the VRT_TRAV_WINDOW=2 leg below must have been able to do -- True: the traversed box is one that gets the
-    32^3-cell bitmap window (every side of 32 cells and more) AND the oracle's list has chunks both inside that window
-    (the settled bit) and outside it (the key read at every visit); False: the box is too small for a window.  The result
-    says which it was (`window`: the window's lowest cell, or None)."""
-    r = cam.render(0, want_ray_rgba=True, **kw)
-    groups = int(r.stats[12]) & 0xffffffff     # (bits 32+: the workgroups that took their rays as tiles)
-    assert (groups > 0) if which.startswith("pool") else (groups == 0), (which, groups)
-    if lookahead is not None:   # did the march step look ahead across chunk borders (march_step_w)?
-        assert (int(r.stats[14]) > 0) == bool(lookahead), (lookahead, int(r.stats[14]))
-    assert np.array_equal(r.rgba_f32.cpu().numpy(), o["pix_mean"].astype(np.float32))
-    assert (r.stats[:8] == o["counters"]).all(), (r.stats[:8], o["counters"])
-    assert np.array_equal(np.array(r.traversed(cs), np.int64).reshape(-1, 3), np.asarray(o["traversed"]).reshape(-1, 3))
-    rays = o["rays"]
-    where = {(int(x), int(y)): i for i, (x, y) in enumerate(r.pixels)}
-    slot = np.array([where[(int(x), int(y))] for x, y in zip(rays["x"], rays["y"])], np.int64) * r.max_samples + rays["s"]
-    packed = (rays["color"][:, 0].astype(np.uint32) | (rays["color"][:, 1].astype(np.uint32) << 8) |
-              (rays["color"][:, 2].astype(np.uint32) << 16) | (rays["alpha"].astype(np.uint32) << 24))
-    got = r.ray_rgba.cpu().numpy().view(np.uint32)
-    assert np.array_equal(got[slot], packed)
-    # ... and once more without the settled-cell bitmap (VRT_TRAV_LDS=0, read at every launch): what traversed boxes too large
-    # for one get -- every visit reads its cell's key, and the kernel instances that compare it after the voxel reads run
-    # -- and, where the window's geometry allows (the pool kernel, a power-of-two run of pixels per hand-out that divides the
-    # height), with the rays handed out as square tiles in Morton order from eight heads (VRT_TILED=2: tile_ticket)
-    os.environ["VRT_TRAV_LDS"], os.environ["VRT_DEFER_VISIT"], os.environ["VRT_TILED"] = "0", "2", "2"   # (2: also over scenes that fit the caches)
-    try:
-        r2 = cam.render(0, want_ray_rgba=True, **kw)
-    finally:
-        del os.environ["VRT_TRAV_LDS"], os.environ["VRT_DEFER_VISIT"], os.environ["VRT_TILED"]
-    assert np.array_equal(r2.ray_rgba.cpu().numpy(), r.ray_rgba.cpu().numpy()) and (r2.stats[:9] == r.stats[:9]).all()
-    assert np.array_equal(r2.traversed_keys.cpu().numpy(), r.traversed_keys.cpu().numpy())
-    # ... with the settled bitmap of boxes too large for one of their own: over the 32^3 cells around the camera only
-    # (VRT_TRAV_WINDOW=2 uses it for every box of at least 32^3 cells; smaller boxes render as before)
-    # -- together with the key comparison behind the voxel reads, as scenes beyond the caches run it
-    os.environ["VRT_TRAV_WINDOW"], os.environ["VRT_DEFER_VISIT"] = "2", "2"
-    try:
-        r4 = cam.render(0, want_ray_rgba=True, **kw)
-    finally:
-        del os.environ["VRT_TRAV_WINDOW"], os.environ["VRT_DEFER_VISIT"]
-    assert np.array_equal(r4.ray_rgba.cpu().numpy(), r.ray_rgba.cpu().numpy()) and (r4.stats[:9] == r.stats[:9]).all()
-    assert np.array_equal(r4.traversed_keys.cpu().numpy(), r.traversed_keys.cpu().numpy())
-    # (could that leg use the window at all?  From the box it was handed, not from anything the library reports)
-    assert r4.trav_origin == r.trav_origin and r4.trav_dims == r.trav_dims
-    r.window = bitmap_window([float(cam.pos.x), float(cam.pos.y), float(cam.pos.z)], cs, r4.trav_origin, r4.trav_dims)
-    if window is not None:
-        assert (r.window is not None) == bool(window), (r4.trav_dims, r.window)
-    if window:
-        inside = window_split(o["traversed"], cs, r4.trav_origin, r.window)
-        assert inside.any() and (~inside).any(), (int(inside.sum()), int((~inside).sum()))
-    # ... and once without the cached ray table (Camera.cache_draws = False): the frame's draws are seeded anew and the march
-    # works out every ray's lens quaternion and life itself instead of reading raygen_tile_kernel's records -- asserted where
-    # the library has such a march (stats[15]: not for resolutions > 2, the look-ahead variant or one record per pixel)
-    s = cam._settings()
-    fused = (not which.endswith("-ahead") and 1 <= int(cam._c_scene(cam._ensure_scene()).max_resolution) <= 2 and
-             (float(s.dof) != 0.0 or float(s.lod_random) != 0.0 or float(s.lod_samples) != 0.0))
-    cached, cam.cache_draws = cam.cache_draws, False
-    try:
-        r3 = cam.render(0, want_ray_rgba=True, **kw)
-    finally:
-        cam.cache_draws = cached
-    if fused:
-        assert int(r3.stats[15]) > 0, r3.stats
-    assert np.array_equal(r3.ray_rgba.cpu().numpy(), r.ray_rgba.cpu().numpy()) and (r3.stats[:9] == r.stats[:9]).all()
-    assert np.array_equal(r3.traversed_keys.cpu().numpy(), r.traversed_keys.cpu().numpy())
-    return r
-
-
-def active(r):
-    rays = r.rays
-    return rays[rays["s"] >= 0]
 
 
 # ------------------------------------------------------------------------------------------------- RNG
@@ -575,32 +500,8 @@ def test_tile_plan_matches_numpy():
     cam = camera_for(sc, settings_store(st), sc.cam_pos, sc.cam_rot, sc.cam_lens)
     for t in range(3):
         cam.render(t, want_image=False, want_f32=False, want_traversed=False)
-        dp = cam._pixel_cache[t][1]
-        px = dp.array.astype(np.int64)
-        L = ol.lib()
-        ost = ol._orc_settings(st)
-        import ctypes as C
-        ns = np.array([L.orc_pixel_samples(C.byref(ost), int(x), int(y)) for x, y in px])
-        seeds = []
-        for (x, y), n in zip(px, ns):
-            seeds += [(1 + x) * (1 + y) * (1 + s) for s in range(n)]
-        distinct = np.unique(np.array(seeds, np.int64))
-        assert dp.n_distinct == len(distinct)
-        raw = dp.plan.cpu().numpy()
-        hdr = raw[:64].view(np.uint64)
-        slots = len(px) * 5
-        assert hdr[1] == len(px) and hdr[2] == slots and hdr[3] == len(distinct)
+        hdr = check_tile_plan(cam._pixel_cache[t][1], st)
         assert hdr[6] == 0                                                      # a third of the window: not the full frame
-        seed_list = raw[64:64 + 4 * slots].view(np.uint32)[: len(distinct)]
-        assert np.array_equal(seed_list.astype(np.int64), distinct)            # sorted, unique
-        off = 64 + ((4 * slots + 255) // 256) * 256
-        idx = raw[off:off + 4 * slots].view(np.uint32).reshape(len(px), 5)
-        for i in range(0, len(px), 37):
-            for s in range(5):
-                if s < ns[i]:
-                    assert seed_list[idx[i, s]] == (1 + px[i, 0]) * (1 + px[i, 1]) * (1 + s)
-                else:
-                    assert idx[i, s] == 0xFFFFFFFF
 
 
 def test_full_frame_resolve_equals_the_list_order_resolve():
