@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define VRT_ABI_VERSION 8
+#define VRT_ABI_VERSION 9
 
 typedef enum {
     VRT_OK = 0,
@@ -259,6 +259,42 @@ int vrt_render_tile(const vrt_scene* scene, const vrt_settings* st, const vrt_ca
                     int32_t fast_draws, const double* d_draw_table, const double* d_ray_table, void* d_workspace,
                     int64_t workspace_bytes, float* d_rgba_f32, uint8_t* d_image_u8, uint32_t* d_ray_rgba, vrt_ray* d_rays,
                     uint64_t* d_stats, const vrt_traversed* trav, void* stream);
+
+/* vrt_render_tile for n_views cameras that share the scene, the settings, the lens, the pixel list, the plan, the draw
+ * table and the ray table (ABI 9): one march launch over n_views times the ray slots (plus its two re-trace launches, a
+ * clear, one set-up launch per 64 views and one resolve) per BATCH instead of per view -- what a small window needs,
+ * whose own march launch leaves the GPU nearly empty (stereo pairs, cube faces, a camera path, many agents'
+ * viewpoints of one world).  Every view's outputs are exactly those of vrt_render_tile with that camera.
+ *   d_cams       DEVICE array of n_views records (a frame stays capturable: nothing is copied or allocated here).  Their
+ *                `lens` fields must all equal the lens the ray table was built for -- the march never reads them, so the
+ *                caller checks this before the upload (Camera.render_views does); positions and rotations must satisfy
+ *                vrt_render_tile's range rule (|pos| + reach < 2^28, |rot| <= 1e3; Camera._check_pose_range restates it
+ *                for the Python layer), which the library cannot test on
+ *                device memory without synchronising (a camera out of range gives a wrong image, never a wild access).
+ *   traversed    HOST array of n_views boxes, or NULL.  Equal `dims`, an `origin` each (checked per view like
+ *                vrt_render_tile's, before any HIP call), and the keys view after view in ONE allocation:
+ *                traversed[v].d_keys == traversed[0].d_keys + v * cells (or all NULL: do not record).  View v's keys are
+ *                (ray slot inside the view) << 12 | resnap_index, so each view's list is the single frame's.
+ *                traversed[0].reset applies to all of them.
+ *   Static seeds and cached tables only -- a batch exists to reuse them: st->seed_nonce != 0, a NULL d_draw_table or
+ *   d_ray_table, or a non-NULL d_rays (no debug records of a batch) returns VRT_ERR_ARG.
+ *   n_views * n_px * max_samples must stay below 2^32; a batch of more than 2^28 ray slots is split into launches at view
+ *   boundaries.
+ * Outputs (each may be NULL), view-major:
+ *   d_rgba_f32   [n_views][n_px][4] float
+ *   d_image_u8   [n_views][height][width][4]
+ *   d_ray_rgba   [n_views][n_px * max_samples] uint32
+ *   d_stats      [VRT_NSTATS] uint64 for the batch as a whole (lanes count events for whatever rays they run; per-view
+ *                counters are not to be had cheaply): words 0..11 equal the SUM of the words the n_views single frames
+ *                report; words 12..15 are 0 (batched launches run neither the ray pool nor the look-ahead).
+ * d_workspace: vrt_views_workspace_bytes() bytes -- the per-sample results of all views, the re-trace tables and the
+ * view records. */
+int vrt_views_workspace_bytes(const vrt_settings* st, int32_t n_views, int64_t n_px, int64_t* bytes);
+int vrt_render_views(const vrt_scene* scene, const vrt_settings* st, const vrt_camera* d_cams, int32_t n_views,
+                     const int32_t* d_pixels_xy, int64_t n_px, const void* d_plan, int64_t n_distinct, int32_t fast_draws,
+                     const double* d_draw_table, const double* d_ray_table, void* d_workspace, int64_t workspace_bytes,
+                     float* d_rgba_f32, uint8_t* d_image_u8, uint32_t* d_ray_rgba, vrt_ray* d_rays, uint64_t* d_stats,
+                     const vrt_traversed* traversed, void* stream);
 
 /* Camera.trace (init.py:37-121) for explicit rays: direction (dir_x, dir_y), detail and the random draws the
  * ray may consume (d_draws[i * n_draws + k] = k-th random.random() of ray i).  d_rays[i].counters[VRT_C_DRAW]

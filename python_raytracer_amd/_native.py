@@ -23,7 +23,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared"] + \
     (["-DVRT_DIAG"] if DIAG else []) + (["-DVRT_DIAG_HIST"] if DIAG_HIST else [])
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 SCENE_TABLE_IS_IDENTITY = 1   # vrt_scene.flags
 SCENE_LAYOUT_DENSE = 2
 ERR_WORKSPACE = -3   # VRT_ERR_WORKSPACE
@@ -130,6 +130,11 @@ def lib():
     L.vrt_render_tile.restype = C.c_int
     L.vrt_render_tile.argtypes = [C.POINTER(VrtScene), C.POINTER(VrtSettings), C.POINTER(VrtCamera), vp, i64, vp, i64,
                                   i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, C.POINTER(VrtTraversed), vp]
+    L.vrt_views_workspace_bytes.restype = C.c_int
+    L.vrt_views_workspace_bytes.argtypes = [C.POINTER(VrtSettings), i32, i64, C.POINTER(i64)]
+    L.vrt_render_views.restype = C.c_int
+    L.vrt_render_views.argtypes = [C.POINTER(VrtScene), C.POINTER(VrtSettings), vp, i32, vp, i64, vp, i64, i32, vp, vp, vp, i64,
+                                   vp, vp, vp, vp, vp, C.POINTER(VrtTraversed), vp]
     L.vrt_draw_table_bytes.restype = C.c_int
     L.vrt_draw_table_bytes.argtypes = [i64, i32, C.POINTER(i64)]
     L.vrt_draw_table_build.restype = C.c_int
@@ -176,6 +181,7 @@ def lib():
 
 EXPORTS = ["vrt_abi_version", "vrt_status_string", "vrt_last_hip_error", "vrt_device_count", "vrt_release_caches", "vrt_voxel_offset",
            "vrt_max_samples", "vrt_plan_bytes", "vrt_plan_build", "vrt_workspace_bytes", "vrt_render_tile",
+           "vrt_views_workspace_bytes", "vrt_render_views",
            "vrt_draw_table_bytes", "vrt_draw_table_build", "vrt_ray_table_bytes", "vrt_ray_table_build",
            "vrt_pow_memo_create", "vrt_occupancy_build", "vrt_canvas_blit", "vrt_world_tables_bytes", "vrt_world_tables_build",
            "vrt_trace_workspace_bytes", "vrt_trace_rays", "vrt_rng_draws",

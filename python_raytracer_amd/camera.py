@@ -593,6 +593,180 @@ class Camera:
                 res.rays = raw.view(np.dtype(nat.RAY_FIELDS, align=True))
         return res
 
+    # ------------------------------------------------------------------ many views of one scene in one launch
+    @staticmethod
+    def _pose_records(poses, lens):
+        """[V, 8] float64 vrt_camera records (pos, rot, lens) of `poses`: a sequence of (pos, rot) pairs, a [V, 7] array
+        (x, y, z, qx, qy, qz, qw) or a [V, 8] array of vrt_camera records, whose lens column must equal `lens` -- the
+        ray table was built for one lens, and the library cannot check records that are already on the device."""
+        if isinstance(poses, np.ndarray):
+            arr = np.asarray(poses, np.float64)
+        else:
+            rows = []
+            for p in poses:
+                pos, rot = p
+                pos = _xyz(pos) if hasattr(pos, "x") else [float(v) for v in pos]
+                rot = [float(rot.x), float(rot.y), float(rot.z), float(rot.w)] if hasattr(rot, "x") else [float(v) for v in rot]
+                if len(pos) != 3 or len(rot) != 4:
+                    raise ValueError("a pose is (pos[3], rot[4])")
+                rows.append(pos + rot)
+            arr = np.asarray(rows, np.float64).reshape(-1, 7)
+        if arr.ndim != 2 or arr.shape[1] not in (7, 8):
+            raise ValueError("poses must be a sequence of (pos, rot) or a [V, 7] array (or [V, 8] vrt_camera records)")
+        if arr.shape[0] == 0:
+            raise ValueError("render_views() needs at least one pose")
+        rec = np.empty((arr.shape[0], 8), np.float64)
+        rec[:, :7] = arr[:, :7]
+        rec[:, 7] = float(lens)
+        if arr.shape[1] == 8 and not np.array_equal(arr[:, 7], rec[:, 7]):
+            raise ValueError("every view of a batch must have the camera's lens (%r): the ray table is built for one lens"
+                             % float(lens))
+        return rec
+
+    def _check_pose_range(self, rec, s):
+        """vrt_render_tile's range rule for a camera (|rot| <= 1e3, |pos| + reach < 2^28), which the library applies to
+        host records only: the cameras of a batch are checked here, before they are uploaded.  (A restatement of the rule in
+        fill_params, csrc/vrt_kernels.hip: keep the two alike.)"""
+        if not np.all(np.isfinite(rec)) or np.abs(rec[:, 3:7]).max() > 1e3:
+            raise ValueError("a pose of the batch is not finite or its rotation exceeds 1e3")
+        q2 = (rec[:, 3:7] ** 2).sum(1)
+        reach = (abs(float(s.dist_max)) + abs(float(s.dist_min)) + 2.0 * int(s.chunk_size) + 2.0) * (8 * q2 + 1)
+        if not np.all(np.abs(rec[:, :3]).max(1) + reach < 2.0 ** 28):
+            raise ValueError("a pose of the batch lies outside the range the march supports: |pos| + reach must stay below 2**28")
+
+    def render_views(self, poses, thread=0, pixels=None, want_image=True, want_f32=True, want_ray_rgba=False,
+                     want_traversed=True, check=True):
+        """Camera.render for many camera poses of one scene with one march launch per batch instead of per view (plus the
+        batch's clear, set-up, two re-trace and resolve launches; vrt_render_views): what a small
+        window needs, whose own launch leaves the GPU nearly empty -- stereo pairs, cube faces, a camera path, many
+        agents' viewpoints.  poses: a sequence of (pos, rot) or a [V, 7] array; lens and settings are the camera's own.
+        Returns one RenderResult per view, bit-identical to render() at that pose: their tensors are views into the
+        batch's, each carries its own traversed box (so traversed() and chunk_update() work per view), and `stats` is the
+        batch's shared block (words 0-11: the sum over the views).  Static settings and cached tables only.
+
+        Inside a stream capture the records' upload (a host-to-device copy) cannot be captured: the device copy of the
+        last batch's records is kept (self._views_cams) and reused for equal poses, so a capture must follow an eager
+        batch with the same poses, and the graph replays those poses only."""
+        torch = self._torch
+        L = nat.lib()
+        s = self._settings()
+        if not s.static:
+            raise ValueError("render_views() needs settings.static: a batch reuses the cached draw and ray tables, which "
+                             "a non-static run re-seeds every frame")
+        if not self.cache_draws:
+            raise ValueError("render_views() needs cache_draws: a batch reuses the cached draw and ray tables")
+        rec = self._pose_records(poses, self.lens)
+        self._check_pose_range(rec, s)
+        n_views = int(rec.shape[0])
+        dev = self._require_device()
+        sc = self._ensure_scene()
+        st = self._c_settings(0)
+        with torch.cuda.device(dev):
+            dp = self._plan_for(self._pixels_tensor(thread, pixels), st)
+        d_px, arr = dp.tensor, dp.array
+        n_px = int(arr.shape[0])
+        csc = self._c_scene(sc)
+        smax = L.vrt_max_samples(C.byref(st))
+        slots = n_px * smax
+        if n_views * slots >= (1 << 32) - 1:
+            raise nat.VrtError("the batch is too large: views * pixels * samples must stay below 2**32 (%d * %d)"
+                               % (n_views, slots))
+        used_draws = self.fast_draws
+        nb = C.c_int64(0)
+        nat.check(L.vrt_views_workspace_bytes(C.byref(st), n_views, n_px, C.byref(nb)), "vrt_views_workspace_bytes")
+        _ensure_pow_memo(torch, dev, s.falloff)
+        ws = self._get_workspace(nb.value)
+        cs = int(s.chunk_size)
+        H, W = int(s.height), int(s.width)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            f32 = torch.empty((n_views, n_px, 4), dtype=torch.float32, device=dev) if want_f32 else None
+            img = (torch.empty if dp.full_frame else torch.zeros)((n_views, H, W, 4), dtype=torch.uint8, device=dev) \
+                if want_image else None
+            rr = torch.empty((n_views, slots), dtype=torch.int32, device=dev) if want_ray_rgba else None
+            stats = torch.empty(nat.NSTATS, dtype=torch.int64, device=dev)   # (the library clears it)
+            # the records' upload is a host-to-device copy, which a stream capture cannot hold: the last batch's device
+            # copy is kept and reused for equal poses (a capture follows a warm-up batch with the poses it captures)
+            ckey = rec.tobytes()
+            hit = getattr(self, "_views_cams", None)
+            if hit is not None and hit[0] == ckey:
+                cams = hit[1]
+            elif torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("render_views() inside a stream capture needs the poses of the batch rendered just before "
+                                   "it (their upload cannot be captured)")
+            else:
+                cams = torch.from_numpy(rec).to(dev)
+                self._views_cams = (ckey, cams)
+            # every view's box by _trav_box's rule for its pose; the velocity bound depends on the rotation, so all of
+            # them get the largest dimensions of the batch (the library wants equal dims and one allocation of keys)
+            trs = keys = None
+            if want_traversed:
+                keep = (self.pos, self.rot)
+                try:
+                    r = 0
+                    for v in range(n_views):
+                        self.rot = quaternion(*rec[v, 3:7])
+                        reach = (float(s.dist_max) + 1.0 + cs / 2.0) * self._velocity_bound()
+                        r = max(r, int(math.ceil(reach / cs)) + 1)
+                finally:
+                    self.pos, self.rot = keep
+                n = 2 * r + 1
+                if n ** 3 > (1 << 28) or n ** 3 * n_views >= (1 << 32):
+                    raise nat.VrtError("the traversed-chunk boxes would need %d x %d^3 cells (dist_max %r, chunk_size %d)"
+                                       % (n_views, n, s.dist_max, cs))
+                keys = torch.empty((n_views, n * n * n), dtype=torch.int64, device=dev)
+                trs = (nat.VrtTraversed * n_views)()
+                for v in range(n_views):
+                    trs[v].origin[:] = [(int(math.floor(p / cs)) - r) * cs for p in rec[v, :3]]
+                    trs[v].dims[:] = [n, n, n]
+                    trs[v].reset = 1
+                    trs[v].d_keys = keys[v].data_ptr()
+            table = self._draw_table_for(dp, st, used_draws)
+            self._order_after_table_builds(dp)   # (the ray table's build reads the draw table)
+            rtab = self._ray_table_for(dp, st, used_draws, table)
+            self._order_after_table_builds(dp)
+            rc = L.vrt_render_views(C.byref(csc), C.byref(st), cams.data_ptr(), n_views, d_px.data_ptr(), n_px,
+                                    dp.plan.data_ptr(), dp.n_distinct, used_draws, table.data_ptr(), rtab.data_ptr(),
+                                    ws.data_ptr(), ws.numel(), f32.data_ptr() if want_f32 else None,
+                                    img.data_ptr() if want_image else None, rr.data_ptr() if want_ray_rgba else None,
+                                    None, stats.data_ptr(), trs if want_traversed else None, stream)
+            nat.check(rc, "vrt_render_views")
+            hstats = None
+            if check:
+                hstats = stats.cpu().numpy()
+                self.last_stats = hstats
+                if hstats[nat.S_RNG_EXHAUSTED]:
+                    if used_draws == 32:
+                        # more rays outran the 32-draw table than the re-trace list holds: render again with 64
+                        self.fast_draws = 64
+                        return self.render_views(rec[:, :7], thread, pixels=dp, want_image=want_image, want_f32=want_f32,
+                                                 want_ray_rgba=want_ray_rgba, want_traversed=want_traversed, check=check)
+                    raise nat.VrtError("%d rays of the batch could not be completed: they outran every draw table; lower "
+                                       "max_bounces or raise material absorption" % int(hstats[nat.S_RNG_EXHAUSTED]))
+                if hstats[nat.S_TRAV_OUTSIDE]:
+                    raise nat.VrtError("%d chunk visits fell outside the traversed boxes (internal bound violated)"
+                                       % int(hstats[nat.S_TRAV_OUTSIDE]))
+                if used_draws == 32 and hstats[nat.S_RNG_RETRACED] * 50 > max(1, hstats[nat.S_RAYS]):
+                    self.fast_draws = 64
+            out = []
+            for v in range(n_views):
+                res = RenderResult()
+                res.max_samples = smax
+                res.pixels = arr
+                res.rgba_f32 = f32[v] if want_f32 else None
+                res.image_u8 = img[v] if want_image else None
+                res.ray_rgba = rr[v] if want_ray_rgba else None
+                if want_traversed:
+                    res.traversed_keys = keys[v]
+                    res.trav_origin = [int(x) for x in trs[v].origin]
+                    res.trav_dims = [int(x) for x in trs[v].dims]
+                else:
+                    res.trav_origin, res.trav_dims = [0, 0, 0], [0, 0, 0]
+                res._stats_dev = stats
+                res.stats = hstats
+                out.append(res)
+        return out
+
     def tile(self, thread, t=0):
         """Reference signature and return triple (init.py:126-150): RGBA8 bytes of the full window (pixels of other
         threads transparent), the traversed chunk list, and the thread index."""

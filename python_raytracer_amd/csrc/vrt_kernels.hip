@@ -745,9 +745,23 @@ __global__ void __launch_bounds__(VRT_BLOCK) world_tables_kernel(int d0, int d1,
 #endif
 #define VRT_CT_LDS_MAX 4096      // chunk tables up to this many cells are copied to LDS (16 KiB)
 #define VRT_TRAV_LDS_MAX 65536   // traversed boxes up to this many cells get a "settled" bitmap in LDS (8 KiB per workgroup)
+// batched views (march_views_kernel, vrt_render_views): the launch's ray slots [ray0, ray0 + n) are those of several cameras,
+// view after view; MarchParams::cam, t_origin_c and the settled bitmap are not used, t_dims is every view's
+struct ViewArgs {
+    const double* view_tab;      // [views][VRT_VIEW_WORDS]: camera position, rotation and traversed-box origin per view
+    int64_t view_cells;          // cells of one view's traversed box: view v's keys begin at t_keys + v * view_cells
+    uint32_t view_slots;         // ray slots per view (ray0 is a multiple of it)
+    int32_t view_lds;            // views whose records are staged in LDS (the others are read from view_tab)
+    int32_t view_lds_off;        // byte offset of the staged records in the dynamic LDS
+    uint32_t view_recip;         // min(floor(2^32 / view_slots), 2^32 - 1): the view of a batch slot without a division (ray_view)
+    uint32_t view_first;         // the launch's first view (ray0 / view_slots): the staged records are its and the following ones'
+};
 struct MarchParams {
     vrt_settings st;
-    vrt_camera cam;
+    union {
+        vrt_camera cam;
+        ViewArgs views;          // (a batched launch has no one camera: its arguments take the place -- the kernels' argument
+    };                           // block, and with it every offset the shipped kernels read at, stays as it was)
     // scene
     int32_t origin_c[3], t_origin_c[3];  // scene box / traversed box origin in chunks (both are multiples of the chunk size)
     int32_t dims[3];
@@ -819,6 +833,11 @@ struct MarchParams {
     uint32_t retrace_cap;            // capacity of retrace_list
     uint32_t list_cap;               // LIST: capacity of `list` (its count may have run past it)
 };
+// one view's record in MarchParams::view_tab: doubles pos[3], rot[4], lens (vrt_camera, as the caller passed it), then the
+// origin of the view's traversed box in chunks as three 32-bit integers and a word of padding (views_setup_kernel)
+#define VRT_VIEW_WORDS 10
+#define VRT_VIEWS_LDS_MAX 96   // views staged in LDS at most: 7.5 KiB, within the 8 KiB a settled bitmap may take (which
+                               // batched launches do without)
 
 // local cell of world cell (f // res) * res for res >= 3 (int // int, exact: |f| < 2^31, res <= 255); rare
 __device__ __noinline__ int3 snap_generic3(int res, int imx, int imy, int imz, int lx, int ly, int lz) {
@@ -993,6 +1012,7 @@ struct Ray {
     uint32_t off;           // offset of the ray in the launch
     uint32_t rowi;          // its draw-table row
     double d0, d1, d2;      // the draws of the ray's next rough hit (from the ray table, then requested after each rough hit)
+    uint32_t view;          // march_views_kernel only: the camera of the batch the ray belongs to (no other kernel touches it)
 };
 
 // lane 0's value in scalar registers (all lanes active)
@@ -1045,6 +1065,7 @@ struct MarchCtx {
     const lds_char* wt;    // world-axis offset tables (P.wt_on): the entry of world cell g on axis a sits at byte
     int wb[3];             // (g << 2) + wb[a], VRT_WT_GUARD guard entries either side of the world included
     unsigned cs3;          // bytes of a chunk's voxel block
+    const lds_char* vw;    // march_views_kernel only: the view records staged in LDS (MarchParams::view_lds of them)
 };
 #define COLD(i) C.cold[(i) + opaque_zero()]
 // MarchParams::snap_flags: the wave-uniform switches of the re-snap.  Every caller re-reads the word from the kernel
@@ -1326,6 +1347,64 @@ __device__ __forceinline__ void resnap_commit(const PT& Q, const MarchCtx& C, Ra
     }
 }
 
+// The re-snap of a batched launch (march_views_kernel only): the ray belongs to view r.view -- the visit goes into that
+// view's key array, relative to that view's box origin, under the key the ray has in a frame of that view alone (its slot
+// inside the view), so every view's list is the single frame's.  No settled bitmap: a workgroup's rays come from several
+// boxes, in no one increasing order -- every visit is the load-then-atomicMin of a box without one.
+template <class PT>
+__device__ __forceinline__ void view_box_origin(const PT& Q, const MarchCtx& C, uint32_t v, int& o0, int& o1, int& o2) {
+    const uint32_t vl = v - Q.views.view_first;
+    if (vl < (uint32_t)Q.views.view_lds) {  // (two loads in two address spaces, never one through a generic pointer: chunk_entry_i)
+        const lds_u32* p = (const lds_u32*)(C.vw + vl * (VRT_VIEW_WORDS * 8) + 64);
+        o0 = (int)p[0]; o1 = (int)p[1]; o2 = (int)p[2];
+    } else {
+        const int4 o = *reinterpret_cast<const int4*>(Q.views.view_tab + (int64_t)v * VRT_VIEW_WORDS + 8);
+        o0 = o.x; o1 = o.y; o2 = o.z;
+    }
+}
+// The view of the ray a lane holds.  FIELD: kept in Ray::view -- one vector register for the ray's whole life; else worked
+// out from the ray's batch slot at every re-snap: the estimate umulhi(slot, floor(2^32 / slots per view)) is at most 2 short
+// of the quotient.  The generic-resolution kernel sits at the 128-register limit and spilled vector registers with the
+// field; the resolution <= 2 kernels have room for it (108 and 115 registers: profiles/views_kernel_resource_usage.txt).
+template <bool FIELD, class PT>
+__device__ __forceinline__ uint32_t ray_view(const PT& Q, const Ray& r) {
+    if constexpr (FIELD) return r.view;
+    const uint32_t b = (uint32_t)(Q.ray0 + r.off), d = Q.views.view_slots;
+    uint32_t q = __umulhi(b, Q.views.view_recip);
+    uint32_t rem = b - q * d;
+    if (rem >= d) { q++; rem -= d; }
+    if (rem >= d) q++;
+    return q;
+}
+template <bool FIELD, class PT>
+__device__ __forceinline__ void resnap_commit_views(const PT& Q, const MarchCtx& C, Ray& r, int fx, int fy, int fz, int fl) {
+    const int ccx = fx >> Q.cs_shift, ccy = fy >> Q.cs_shift, ccz = fz >> Q.cs_shift;
+    r.nm4x = -(ccx << (Q.cs_shift + 2));
+    r.nm4y = -(ccy << (Q.cs_shift + 2));
+    r.nm4z = -(ccz << (Q.cs_shift + 2));
+    const uint32_t view = ray_view<FIELD>(Q, r);
+    int vo0, vo1, vo2;
+    view_box_origin(Q, C, view, vo0, vo1, vo2);
+    const uint64_t tkey = ((uint64_t)((uint32_t)(Q.ray0 + r.off) - view * Q.views.view_slots) << 12) | (uint64_t)(r.resnaps < 4095 ? r.resnaps : 4095);
+    // (the box's dimensions from the arguments, not from MarchCtx::td: the three vector registers of those per-lane copies
+    // are what the generic-resolution instance, at the 128-register limit, would spill)
+    const int tci = trav_cell((fl & CF_HAS_KEYS) != 0, ccx, ccy, ccz, vo0, vo1, vo2, Q.t_dims[0], Q.t_dims[1], Q.t_dims[2]);
+    r.entry = chunk_entry_i(Q, C.ct, ccx - C.oc[0], ccy - C.oc[1], ccz - C.oc[2], C.dm[0], C.dm[1], C.dm[2], (fl & CF_CT_LDS) != 0,
+                            (fl & CF_CT_IDENTITY) != 0);
+    // (a 32-bit index from the base of all the views' keys -- vrt_render_views keeps views * cells below 2^32: the base stays in
+    // scalar registers, no 64-bit pointer per lane)
+    const uint32_t ki = view * (uint32_t)Q.views.view_cells + (uint32_t)tci;
+    uint64_t tcur = 0;
+    if (tci >= 0) tcur = Q.t_keys[ki];
+    r.boff = ((r.entry & 0xffffffu) - 1u) << (3 * Q.cs_shift);
+    if (tci >= 0) {
+        if (tkey < tcur) atomicMin((unsigned long long*)&Q.t_keys[ki], (unsigned long long)tkey);
+    } else if (tci == -2) {
+        atomicAdd((unsigned long long*)&Q.stats[VRT_S_TRAV_OUTSIDE], 1ull);
+    }
+    r.resnaps++;
+}
+
 // `after`: a value that only exists once the caller's voxel reads are back.  The key passes through an empty statement that
 // names it, so the comparison (and the wait for the key) cannot be scheduled ahead of those reads
 template <bool BM, class PT>
@@ -1446,6 +1525,87 @@ __device__ __forceinline__ bool take_ray(const MarchParams& P, const MarchCtx& C
     return true;
 }
 
+// take_ray for a batched launch (march_views_kernel): ray k of the launch is slot `ray` of view `v` -- the plan, the ray table
+// and the pixel list are the view's own (every view shares them) and are read with the slot inside the view; the results and
+// the re-trace list are the batch's and keep the batch offset (r.off).  The camera comes from the view's record (staged in
+// LDS for the first MarchParams::view_lds views, else from memory), not from the COLD_POS / COLD_ROT scalars.  Static seeds
+// and both cached tables are required (vrt_render_views), so P.per_pixel is 0 or 1 and every slot has a plan row.
+template <bool LIST, int SEED>
+__device__ __forceinline__ bool take_ray_views(const MarchParams& P, const MarchCtx& C, int64_t k, Ray& r) {
+    const auto& Q = fresh_args(P);  // (see fresh_args)
+    const int64_t off = LIST ? (int64_t)Q.list[k] : k;
+    const uint32_t bray = (uint32_t)(Q.ray0 + off);  // slot in the batch (< 2^32: vrt_render_views)
+    const uint32_t v = bray / Q.views.view_slots;
+    const uint32_t ray = bray - v * Q.views.view_slots;    // slot inside the view
+    const int64_t rowi = LIST ? k : (int64_t)Q.ray_seedidx[ray];
+    if (LIST && SEED != 0) {
+        const uint32_t p = ray / (uint32_t)Q.g.smax;
+        const uint64_t seed = ray_seed(Q.st, Q.g.smax, Q.g.pixels[2 * (int64_t)p], Q.g.pixels[2 * (int64_t)p + 1], (int)(ray - p * (uint32_t)Q.g.smax));
+        double* row = const_cast<double*>(Q.draws) + rowi * Q.draw_stride;
+        if (SEED == 1) mt_seed_draws<true>(seed, D_SLOW_DEV, row);
+        else mt_full_draws(seed, D_FULL_DEV, row);
+        __threadfence();  // (the row is read back below and by the ray's hits)
+    }
+    double life, ox, oy, oz, ow, t0, t1, t2;
+    if (Q.per_pixel) {
+        // the pixel's record (d0 = its sample count); the ray's first-hit draws come from the draw table
+        const uint32_t px = ray / (uint32_t)Q.g.smax;
+        const RayRecord rec = Q.tab.rec[px];
+        ox = rec.ox; oy = rec.oy; oz = rec.oz; ow = rec.ow;
+        life = (int)(ray - px * (uint32_t)Q.g.smax) < (int)rec.d0 ? rec.life : -1.0;
+        t0 = t1 = t2 = 0.5;
+        if (life >= 0.0) {  // (an unused sample slot has no draw row: its index in the plan is 0xFFFFFFFF)
+            const double* row = Q.draws + rowi * Q.draw_stride + Q.first_draw;
+            t0 = row[0];
+            t1 = row[1];
+            t2 = row[2];
+        }
+    } else {
+        const RayRecord rec = Q.tab.rec[ray];
+        life = rec.life; ox = rec.ox; oy = rec.oy; oz = rec.oz; ow = rec.ow;
+        t0 = rec.d0; t1 = rec.d1; t2 = rec.d2;
+    }
+    if (life < 0.0) {  // unused sample slot of the tile
+        if (Q.ray_rgba) Q.ray_rgba[bray] = 0;
+        return false;
+    }
+    r.off = (uint32_t)off;
+    r.view = v;  // (dropped by the compiler in the instances that work it out again: ray_view)
+    double cq0, cq1, cq2, cq3, cpx, cpy, cpz;
+    const uint32_t vl = v - Q.views.view_first;
+    if (vl < (uint32_t)Q.views.view_lds) {
+        const lds_f64* c = (const lds_f64*)(C.vw + vl * (VRT_VIEW_WORDS * 8));
+        cpx = c[0]; cpy = c[1]; cpz = c[2];
+        cq0 = c[3]; cq1 = c[4]; cq2 = c[5]; cq3 = c[6];
+    } else {
+        const double* c = Q.views.view_tab + (int64_t)v * VRT_VIEW_WORDS;
+        cpx = c[0]; cpy = c[1]; cpz = c[2];
+        cq0 = c[3]; cq1 = c[4]; cq2 = c[5]; cq3 = c[6];
+    }
+    const double dist_min = COLD(COLD_DIST_MIN);
+    camera_forward(cq0, cq1, cq2, cq3, ox, oy, oz, ow, r.vx, r.vy, r.vz);  // init.py:44-45
+    r.life = life;
+    // init.py:50-59
+    r.px = cpx + r.vx * dist_min;
+    r.py = cpy + r.vy * dist_min;
+    r.pz = cpz + r.vz * dist_min;
+    r.step = 0;
+    r.bounces = 0;
+    r.energy = 0;
+    r.color = 0;
+    // chunk_min = chunk_max = vec3(0, 0, 0), chunk = None (init.py:46-47): see take_ray
+    r.nm4x = r.nm4y = r.nm4z = (int)0x80000000u;
+    r.entry = 0;
+    r.boff = 0;
+    r.resnaps = 0;
+    r.ndraw = Q.first_draw;
+    r.rowi = (uint32_t)rowi;
+    r.d0 = t0;
+    r.d1 = t1;
+    r.d2 = t2;
+    return true;
+}
+
 // MARCH: phase A of the reference loop (init.py:66-77, 114-116) for a lane in LANE_MARCH -- loop condition, chunk
 // re-snap, the voxel of this position and speculatively of the next SPEC - 1, advance.  Leaves the lane in LANE_MARCH,
 // LANE_HIT (a voxel was found: its material sits in the colour word's top byte) or LANE_ENDED.
@@ -1470,7 +1630,9 @@ __device__ __forceinline__ decltype(auto) march_args(const MarchParams& P) {
 }
 // DEFER: the launch's traversed box has no settled bitmap -- the key reads of its re-snaps are compared after the voxel
 // reads have been issued (resnap_commit<DEFER>)
-template <int SPEC, int RESMODE, bool RECORD, int LK, bool FRESH = VRT_FRESH_MARCH, int DEFER = 0>
+// VIEWS: the launch's rays belong to several cameras (march_views_kernel; resnap_commit_views) -- 1: a ray's view is kept in
+// Ray::view, 2: it is worked out from the ray's slot (ray_view)
+template <int SPEC, int RESMODE, bool RECORD, int LK, bool FRESH = VRT_FRESH_MARCH, int DEFER = 0, int VIEWS = 0>
 __device__ __forceinline__ void march_step(const MarchParams& P, const MarchCtx& C, Ray& r, int& state, int32_t (&cnt)[C_NLOCAL],
                                            uint64_t wmin_key, LkState& lk, SeenList<RECORD>& sl, DgLane& dg) {
     (void)lk; (void)sl; (void)dg;
@@ -1512,7 +1674,8 @@ __device__ __forceinline__ void march_step(const MarchParams& P, const MarchCtx&
             if (l4or == 0x80000000u) outside = !(r.px == 0.0 && r.py == 0.0 && r.pz == 0.0);
         }
         if (outside) {
-            resnap_commit<RECORD, FRESH, DEFER>(Q, C, r, fx, fy, fz, wmin_key, sl, fl, &pend);
+            if constexpr (VIEWS != 0) resnap_commit_views<VIEWS == 1>(Q, C, r, fx, fy, fz, fl);
+            else resnap_commit<RECORD, FRESH, DEFER>(Q, C, r, fx, fy, fz, wmin_key, sl, fl, &pend);
             l4x = (int)(((unsigned)fx << 2) + (unsigned)r.nm4x);
             l4y = (int)(((unsigned)fy << 2) + (unsigned)r.nm4y);
             l4z = (int)(((unsigned)fz << 2) + (unsigned)r.nm4z);
@@ -2387,6 +2550,8 @@ __device__ __forceinline__ void diag_flush(DgLane& dg, unsigned long long dg_sta
 // 1 and 2 are kept for measurement (VRT_LOOKUP=1|2, profiles/r02_v7_lookup_variants.md); a hit reads the byte in both.
 // W: the scene's blocks lie in table order and the march step looks ahead across chunk borders (march_step_w)
 // DEFER: see march_step
+// (march_views_kernel below repeats this kernel's refill / march / hit / ended loop for batched launches, so that this
+// kernel's code generation stays as it is: a fix to the hand-out loop belongs in both.)
 template <int SPEC, int RESMODE, bool RECORD, bool LIST, int LK = 0, int PERPIX = (RECORD || LIST) ? 4 : 0, bool W = false, bool DEFER = false, int SEED = 0>
 __global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) march_kernel(MarchParams P) {
     static_assert(SPEC >= 4 && SPEC <= 16, "speculation depth");
@@ -2561,6 +2726,137 @@ __global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) march_kernel(Ma
 #endif
     if (W && threadIdx.x == 0) atomicAdd(&S.stats[VRT_S_LOOKAHEAD_GROUPS], 1ull);
     if (!LIST && threadIdx.x == 0 && PERPIX == 3) atomicAdd(&S.stats[VRT_S_RAYGEN_GROUPS], 1ull);
+    march_epilogue<LIST>(P, S);
+}
+
+// ---- march_views_kernel: march_kernel's skeleton for a batch of cameras over one scene (vrt_render_views) ---------------
+// A small window leaves a march launch nearly empty, and the end of a launch costs the same whatever its size: V views of
+// one world -- stereo pairs, cube faces, a camera path -- are marched as ONE march launch over V times the ray slots.  Plan, draw
+// table and ray table do not depend on the camera's position or rotation, so every view shares them; what differs per view
+// is a record of VRT_VIEW_WORDS doubles (camera, traversed-box origin) and a key array.  A lane that takes slot k of the batch
+// works out its view and its slot inside it (take_ray_views), keeps the view in Ray::view, and the re-snap records the visit
+// in that view's box under the key the ray has in a frame of that view alone (resnap_commit_views): every view's list is
+// the single frame's.  A workgroup holds rays of several views, so there is no settled bitmap (its bound assumes one box
+// and one increasing ray order): every visit is the load-then-atomicMin of a box without one.  The bodies are the shared
+// ones; LIST / SEED are the two re-trace tiers (the list holds batch offsets).
+template <int SPEC, int RESMODE, bool LIST, int SEED = 0>
+__global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) march_views_kernel(MarchParams P) {
+    static_assert(SPEC >= 4 && SPEC <= 16, "speculation depth");
+    __shared__ MarchShared S;
+    extern __shared__ __align__(16) unsigned char s_dyn[];
+    if (LIST && *P.list_count == 0) return;  // the usual case: no ray ran out of draws
+    MarchCtx C;
+    march_prologue<false>(P, S, s_dyn, C);
+    {
+        double* s_views = reinterpret_cast<double*>(s_dyn + P.views.view_lds_off);
+        const double* first = P.views.view_tab + (int64_t)P.views.view_first * VRT_VIEW_WORDS;
+        for (int i = threadIdx.x; i < P.views.view_lds * VRT_VIEW_WORDS; i += VRT_BLOCK) s_views[i] = first[i];
+        C.vw = (const lds_char*)s_views;
+    }
+    __syncthreads();
+
+    const int64_t count = LIST ? (int64_t)(*P.list_count < P.list_cap ? *P.list_count : P.list_cap) : P.n;
+    const int64_t chunk = P.chunk;
+    int64_t next = 0, range_end = 0;
+    bool more = true;  // the launch-wide counter may still have rays
+    if (chunk == 0) {  // static contiguous range per wave
+        const int64_t n_waves = (int64_t)gridDim.x * (VRT_BLOCK / VRT_WAVE);
+        const int64_t wave = (int64_t)blockIdx.x * (VRT_BLOCK / VRT_WAVE) + (threadIdx.x >> 6);
+        int64_t per = (count + n_waves - 1) / n_waves;
+        per = (per + 7) & ~(int64_t)7;
+        next = wave * per;
+        range_end = next + per < count ? next + per : count;
+        more = false;
+    }
+
+    Ray r;
+    r.px = r.py = r.pz = r.vx = r.vy = r.vz = 0;
+    r.step = r.life = r.bounces = r.energy = 0;
+    r.nm4x = r.nm4y = r.nm4z = 0;
+    r.entry = 0;
+    r.boff = 0;
+    r.color = 0;
+    r.ndraw = r.resnaps = 0;
+    r.off = 0;
+    r.rowi = 0;
+    r.d0 = r.d1 = r.d2 = 0.5;
+    r.view = 0;
+    int state = LANE_IDLE;
+    int32_t cnt[C_NLOCAL];   // events of the current ray
+#pragma unroll
+    for (int j = 0; j < C_NLOCAL; j++) cnt[j] = 0;
+    SeenList<false> sl;
+    sl.n = 0;
+    LkState lk;
+    lk.okey = ~0u;
+    lk.oword = 0;
+    lk.brick_slot = nullptr;
+    DgLane dg;
+#ifdef VRT_DIAG
+    __shared__ unsigned long long s_dg[VRT_BLOCK / VRT_WAVE][DG_N];  // (the bodies count into it; a batched launch reports nothing)
+    dg.acc = (__attribute__((address_space(3))) unsigned long long*)&s_dg[threadIdx.x >> 6][0];
+    if ((threadIdx.x & 63) == 0)
+        for (int j = 0; j < DG_N; j++) dg.acc[j] = 0;
+    dg.brick = ~0u;
+    dg.bv = 0;
+#endif
+
+    for (;;) {
+        // ------------------------------------------------------------------ refill idle lanes
+        unsigned long long idle_mask = __ballot(state == LANE_IDLE);
+        while (idle_mask != 0ull && (next < range_end || more)) {
+            if (next >= range_end) {  // take the next chunk (one atomic per wave per chunk)
+                unsigned long long base = 0;
+                if ((threadIdx.x & 63) == 0) base = atomicAdd(P.queue_head, (unsigned long long)chunk);
+                base = wave_first_u64(base);
+                if ((int64_t)base >= count) {
+                    more = false;
+                    break;
+                }
+                next = (int64_t)base;
+                range_end = next + chunk < count ? next + chunk : count;
+            }
+            const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(idle_mask >> 32),
+                                                            __builtin_amdgcn_mbcnt_lo((unsigned)idle_mask, 0u));
+            const int64_t k = next + rank;
+            next += __popcll(idle_mask);
+            if (state == LANE_IDLE && k < range_end) {
+                if (take_ray_views<LIST, SEED>(P, C, k, r)) {
+#pragma unroll
+                    for (int j = 0; j < C_NLOCAL; j++) cnt[j] = 0;
+                    state = LANE_MARCH;
+                }
+            }
+            idle_mask = __ballot(state == LANE_IDLE);
+        }
+        if (__ballot(state != LANE_IDLE) == 0ull) break;  // range exhausted and every lane finished
+
+        // ------------------------------------------------------------------ MARCH steps (phase A)
+        int iters = 0;
+        for (;;) {
+            const int n_march = (int)__popcll(__ballot(state == LANE_MARCH));
+            const int n_hit = (int)__popcll(__ballot(state == LANE_HIT));
+            const int n_end = (int)__popcll(__ballot(state >= LANE_ENDED));
+            if (n_march == 0 || n_hit >= P.t_hit || n_end >= P.t_end) break;
+            if (iters >= P.max_iters && n_hit + n_end > 0) break;
+            iters++;
+            if (state == LANE_MARCH) march_step<SPEC, RESMODE, false, 0, VRT_FRESH_MARCH, 0, RESMODE == 2 ? 2 : 1>(P, C, r, state, cnt, 0ull, lk, sl, dg);
+        }
+        const bool none_marching = __ballot(state == LANE_MARCH) == 0ull;
+        const bool capped = iters >= P.max_iters;
+
+        // ------------------------------------------------------------------ HIT (phase B: init.py:78-116)
+        const bool serve_hit = none_marching || capped || (int)__popcll(__ballot(state == LANE_HIT)) >= P.t_hit;
+        if (serve_hit && state == LANE_HIT) hit_body<RESMODE, LIST>(P, C, r, state, cnt, dg);
+
+        // ------------------------------------------------------------------ ENDED: background, outputs
+        const bool serve_ended = none_marching || capped || (int)__popcll(__ballot(state >= LANE_ENDED)) >= P.t_end ||
+                                 __ballot(state == LANE_MARCH) == 0ull;
+        if (serve_ended && state >= LANE_ENDED) {
+            ended_body<false, true>(P, C, r, state, cnt, 0, S.stats);
+            state = LANE_IDLE;
+        }
+    }
     march_epilogue<LIST>(P, S);
 }
 
@@ -3017,9 +3313,8 @@ __device__ __forceinline__ uint32_t resolve_pixel(const vrt_settings& st, int sm
 // consecutive threads write 4 bytes W * 4 bytes apart.  When the list is the whole window in that order (the plan
 // knows: PlanHeader.full_frame) a workgroup takes a 16 x 16 pixel tile instead, reads its 16 columns' samples, and
 // writes the image rows from an LDS tile, 64 contiguous bytes at a time (config 3: 0.18 -> 0.1 ms).
-__global__ void __launch_bounds__(VRT_BLOCK) resolve_kernel(vrt_settings st, TileGeom g, const PlanHeader* hdr,
-                                                            const uint32_t* ray_rgba, float* rgba_f32, uint8_t* image_u8) {
-    __shared__ uint32_t s_tile[16][17];
+__device__ __forceinline__ void resolve_body(const vrt_settings& st, const TileGeom& g, const PlanHeader* hdr, const uint32_t* ray_rgba,
+                                             float* rgba_f32, uint8_t* image_u8, uint32_t (&s_tile)[16][17]) {
     if (hdr->full_frame) {
         const int tiles_y = (st.height + 15) / 16;
         const int bx = (int)(blockIdx.x / tiles_y), by = (int)(blockIdx.x % tiles_y);
@@ -3048,6 +3343,22 @@ __global__ void __launch_bounds__(VRT_BLOCK) resolve_kernel(vrt_settings st, Til
     const uint32_t px = resolve_pixel(st, g.smax, ray_rgba, p, x, y, mean);
     if (rgba_f32) reinterpret_cast<float4*>(rgba_f32)[p] = mean;
     if (image_u8) reinterpret_cast<uint32_t*>(image_u8)[(int64_t)y * st.width + x] = px;
+}
+__global__ void __launch_bounds__(VRT_BLOCK) resolve_kernel(vrt_settings st, TileGeom g, const PlanHeader* hdr,
+                                                            const uint32_t* ray_rgba, float* rgba_f32, uint8_t* image_u8) {
+    __shared__ uint32_t s_tile[16][17];
+    resolve_body(st, g, hdr, ray_rgba, rgba_f32, image_u8, s_tile);
+}
+// ... for the views of a batch (vrt_render_views) in one launch: blockIdx.y walks the views, whose results, means and images
+// lie view after view
+__global__ void __launch_bounds__(VRT_BLOCK) resolve_views_kernel(vrt_settings st, TileGeom g, const PlanHeader* hdr, int n_views,
+                                                                  const uint32_t* ray_rgba, float* rgba_f32, uint8_t* image_u8) {
+    __shared__ uint32_t s_tile[16][17];
+    for (int v = blockIdx.y; v < n_views; v += gridDim.y) {
+        resolve_body(st, g, hdr, ray_rgba + (int64_t)v * g.n_px * g.smax, rgba_f32 ? rgba_f32 + (int64_t)v * g.n_px * 4 : nullptr,
+                     image_u8 ? image_u8 + (int64_t)v * st.height * st.width * 4 : nullptr, s_tile);
+        __syncthreads();  // (the tile is written again for the next view)
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3631,6 +3942,8 @@ static int fill_params(MarchParams& P, const vrt_scene* sc, const vrt_settings* 
         return VRT_ERR_ARG;
     if (sc->n_slots < 0 || sc->n_slots >= (1 << 24)) return VRT_ERR_ARG;
     if (!d_stats) return VRT_ERR_ARG;
+    // (Camera._check_pose_range in camera.py restates this rule for the cameras of a batch, which are device records the
+    // library cannot read here: keep the two alike.)
     // The march keeps 4 * floor(pos) in 32-bit integers: the camera and everything a ray can reach must stay inside
     // +-2^28.  |vel|_inf <= 8 |rot|^2 + 1 for the reference's (not norm-preserving) quaternion product applied to a
     // unit lens quaternion (lib.py:353-358, 372-376); a ray travels at most dist_max - dist_min plus one void-skip step.
@@ -4034,6 +4347,82 @@ static inline int res_mode(const vrt_scene* sc) {
     return sc->max_resolution == 1 ? 0 : (sc->max_resolution == 2 ? 1 : 2);
 }
 
+// ---- batched views (vrt_render_views) --------------------------------------------------------------------------------
+// The cameras are on the device, the origins of the traversed boxes on the host, and a frame neither copies nor allocates:
+// the origins travel as kernel arguments, 64 views per launch, and meet the cameras in the view table
+struct ViewOrigins { int32_t o[64][4]; };
+__global__ void __launch_bounds__(64) views_setup_kernel(const vrt_camera* cams, ViewOrigins org, int v0, int n, double* view_tab) {
+    const int t = threadIdx.x;
+    if (t >= n) return;
+    const double* c = reinterpret_cast<const double*>(cams + v0 + t);
+    double* out = view_tab + (int64_t)(v0 + t) * VRT_VIEW_WORDS;
+    for (int i = 0; i < 8; i++) out[i] = c[i];
+    *reinterpret_cast<int4*>(out + 8) = make_int4(org.o[t][0], org.o[t][1], org.o[t][2], 0);
+}
+struct ViewsLayout {
+    int64_t slots;       // ray slots per view
+    int64_t per_launch;  // views per march launch
+    int64_t slow_cap, full_cap;
+    int64_t off_slow, off_full, off_rgba, off_list, off_list_full, off_count, off_pow, off_views, total;
+};
+// launches end at view boundaries: as many whole views as fit batch_rays() slots, at least one
+static ViewsLayout views_layout(const vrt_settings* st, int64_t n_views, int64_t n_px) {
+    ViewsLayout w;
+    w.slots = n_px * vrt_max_samples(st);
+    w.per_launch = w.slots > 0 ? batch_rays() / w.slots : n_views;
+    if (w.per_launch < 1) w.per_launch = 1;
+    if (w.per_launch > n_views) w.per_launch = n_views;
+    const int64_t batch = w.per_launch * w.slots;
+    int64_t o = 0;
+    auto take = [&](int64_t bytes) { int64_t r = o; o += align256(bytes); return r; };
+    w.slow_cap = batch / 64;  // (as ws_layout)
+    if (w.slow_cap < SLOW_CAP_MIN) w.slow_cap = batch < SLOW_CAP_MIN ? batch : SLOW_CAP_MIN;
+    if (w.slow_cap > SLOW_CAP_MAX) w.slow_cap = SLOW_CAP_MAX;
+    w.off_slow = take(w.slow_cap * VRT_SLOW_STRIDE * 8);
+    w.full_cap = w.slow_cap < FULL_CAP ? w.slow_cap : FULL_CAP;
+    w.off_full = take(w.full_cap * D_FULL_DEV * 8);
+    w.off_rgba = take(n_views * w.slots * 4);
+    w.off_list = take(w.slow_cap * 4);
+    w.off_list_full = take(w.full_cap * 4);
+    w.off_count = take(256 + 8 * 128);
+    w.off_pow = take(2 * VRT_PW_SLOTS * 8);
+    w.off_views = take(n_views * VRT_VIEW_WORDS * 8);
+    w.total = o;
+    return w;
+}
+// dynamic LDS of a batched launch: march_lds (no settled bitmap) | the view records that fit -- VRT_VIEWS_LDS_MAX of them,
+// fewer when materials and chunk table leave less than VRT_WAVES_PER_SIMD workgroups per CU would need
+static inline size_t views_lds(MarchParams& P, int64_t n_views) {  // n_views: the views of this launch
+    P.trav_words = 0;
+    P.bm_window = -1;
+    P.wt_on = 0;
+    size_t n = march_lds(P, false, false);
+    n = (n + 15) & ~(size_t)15;
+    const int64_t room = 160 * 1024 / VRT_WAVES_PER_SIMD - 2 * 1024 - (int64_t)sizeof(MarchShared) - (int64_t)n;
+    int64_t fit = room / (VRT_VIEW_WORDS * 8);
+    if (fit > VRT_VIEWS_LDS_MAX) fit = VRT_VIEWS_LDS_MAX;
+    if (fit > n_views) fit = n_views;
+    if (fit < 0) fit = 0;
+    P.views.view_lds = (int32_t)fit;
+    P.views.view_lds_off = (int32_t)n;
+    return n + (size_t)fit * VRT_VIEW_WORDS * 8;
+}
+// the frame's march of a batch (LIST false) and its two re-trace tiers (P.list_seed 1 | 2)
+template <bool LIST>
+static void launch_march_views(MarchParams P, int grid, int resmode, int64_t n_views, hipStream_t stream) {
+    const size_t lds = views_lds(P, n_views);
+    if (LIST) {  // one generic variant, like march_kernel's re-traces
+        if (P.list_seed == 1) hipLaunchKernelGGL((march_views_kernel<VRT_SPEC, 2, LIST, LIST ? 1 : 0>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
+        else hipLaunchKernelGGL((march_views_kernel<VRT_SPEC, 2, LIST, LIST ? 2 : 0>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
+    } else if (resmode == 0) {
+        hipLaunchKernelGGL((march_views_kernel<VRT_SPEC_DEEP, 0, false>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
+    } else if (resmode == 1) {
+        hipLaunchKernelGGL((march_views_kernel<VRT_SPEC_DEEP, 1, false>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
+    } else {
+        hipLaunchKernelGGL((march_views_kernel<VRT_SPEC, 2, false>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
+    }
+}
+
 extern "C" {
 
 int vrt_draw_table_bytes(int64_t n_distinct, int32_t fast_draws, int64_t* bytes) {
@@ -4272,6 +4661,173 @@ int vrt_render_tile(const vrt_scene* scene, const vrt_settings* st, const vrt_ca
         const int64_t rgrid = grid_for(n_px) > tiles ? grid_for(n_px) : tiles;
         hipLaunchKernelGGL(resolve_kernel, dim3((unsigned)rgrid), dim3(VRT_BLOCK), 0, stream, *st, g, (const PlanHeader*)d_plan, rgba,
                            d_rgba_f32, d_image_u8);
+    }
+    HIP_TRY(hipGetLastError());
+    return VRT_OK;
+}
+
+int vrt_views_workspace_bytes(const vrt_settings* st, int32_t n_views, int64_t n_px, int64_t* bytes) {
+    if (check_settings(st) != VRT_OK || n_views < 1 || n_px < 0 || !bytes) return VRT_ERR_ARG;
+    if ((int64_t)n_views * n_px * vrt_max_samples(st) >= 4294967295ll) return VRT_ERR_ARG;
+    *bytes = views_layout(st, n_views, n_px).total;
+    return VRT_OK;
+}
+
+int vrt_render_views(const vrt_scene* scene, const vrt_settings* st, const vrt_camera* d_cams, int32_t n_views,
+                     const int32_t* d_pixels_xy, int64_t n_px, const void* d_plan, int64_t n_distinct, int32_t fast_draws,
+                     const double* d_draw_table, const double* d_ray_table, void* d_workspace, int64_t workspace_bytes,
+                     float* d_rgba_f32, uint8_t* d_image_u8, uint32_t* d_ray_rgba, vrt_ray* d_rays, uint64_t* d_stats,
+                     const vrt_traversed* traversed, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!d_cams || n_views < 1) return VRT_ERR_ARG;
+    if (d_rays) return VRT_ERR_ARG;                                      // no debug records of a batch
+    if (!st || st->seed_nonce != 0) return VRT_ERR_ARG;                  // static seeds only: a batch exists to reuse the cached tables
+    if (!d_draw_table || !d_ray_table) return VRT_ERR_ARG;
+    // the scene and settings checks of a frame; the cameras are on the device (their range is the caller's to check: the
+    // march itself reads voxels through a bounds-checked buffer and tests every table and box index it forms)
+    vrt_camera cam0;
+    for (int a = 0; a < 3; a++) cam0.pos[a] = 0.0;
+    cam0.rot[0] = cam0.rot[1] = cam0.rot[2] = 0.0;
+    cam0.rot[3] = 1.0;
+    cam0.lens = 0.0;
+    MarchParams P;
+    int rc = fill_params(P, scene, st, &cam0, nullptr, d_stats);
+    if (rc != VRT_OK) return rc;
+    if (n_px < 0 || (n_px > 0 && !d_pixels_xy) || !d_workspace || !d_plan) return VRT_ERR_ARG;
+    if (!plan_supported(st)) return VRT_ERR_ARG;
+    const int smax = vrt_max_samples(st);
+    const int64_t slots = n_px * smax;
+    if ((int64_t)n_views * slots >= 4294967295ll) return VRT_ERR_ARG;
+    if (n_distinct < 0 || n_distinct > slots || !fast_draws_ok(fast_draws)) return VRT_ERR_ARG;
+    // the traversed boxes: equal dimensions, an origin each, the keys view after view in one allocation
+    ViewOrigins org;
+    uint64_t* keys = nullptr;
+    int64_t tcells = 0;
+    if (traversed && traversed[0].d_keys) {
+        tcells = 1;
+        for (int a = 0; a < 3; a++) {
+            if (traversed[0].dims[a] <= 0) return VRT_ERR_ARG;
+            tcells *= traversed[0].dims[a];
+            if (tcells >= (1ll << 31)) return VRT_ERR_ARG;
+        }
+        if (tcells * n_views >= (1ll << 32)) return VRT_ERR_ARG;  // (resnap_commit_views indexes all the views' keys with 32 bits)
+        for (int v = 0; v < n_views; v++) {
+            const vrt_traversed& t = traversed[v];
+            if (t.d_keys != traversed[0].d_keys + (int64_t)v * tcells) return VRT_ERR_ARG;
+            for (int a = 0; a < 3; a++) {
+                if (t.dims[a] != traversed[0].dims[a] || (t.origin[a] % st->chunk_size) != 0) return VRT_ERR_ARG;
+                if (t.origin[a] < -(1ll << 28) || t.origin[a] + (int64_t)t.dims[a] * st->chunk_size > (1ll << 28)) return VRT_ERR_ARG;
+            }
+        }
+        keys = traversed[0].d_keys;
+        for (int a = 0; a < 3; a++) P.t_dims[a] = traversed[0].dims[a];
+    } else if (traversed) {
+        for (int v = 1; v < n_views; v++)
+            if (traversed[v].d_keys) return VRT_ERR_ARG;  // (all of the views record, or none)
+    }
+    P.t_keys = keys;
+    P.views.view_cells = tcells;
+    ViewsLayout w = views_layout(st, n_views, n_px);
+    if (workspace_bytes < w.total) return VRT_ERR_WORKSPACE;
+    char* ws = (char*)d_workspace;
+    double* t_slow = (double*)(ws + w.off_slow);
+    uint32_t* rgba = d_ray_rgba ? d_ray_rgba : (uint32_t*)(ws + w.off_rgba);
+    uint32_t* list = (uint32_t*)(ws + w.off_list);
+    uint32_t* count = (uint32_t*)(ws + w.off_count);
+    double* view_tab = (double*)(ws + w.off_views);
+    unsigned long long* pow_global = device_pow_memo(1 + st->falloff);
+    const bool frame_memo = pow_global == nullptr;
+    if (frame_memo) pow_global = (unsigned long long*)(ws + w.off_pow);
+    {   // what frame_begin clears, with the keys of every view
+        const int64_t n_keys = keys && traversed[0].reset ? tcells * n_views : 0;
+        const int64_t kb = (n_keys + VRT_BLOCK * 8 - 1) / (VRT_BLOCK * 8);
+        hipLaunchKernelGGL(frame_begin_kernel, dim3((unsigned)(kb < 1 ? 1 : (kb > 1024 ? 1024 : kb))), dim3(VRT_BLOCK), 0, stream, (uint32_t*)d_stats,
+                           (int)(2 * VRT_NSTATS), count, n_px > 0 ? 64 + 8 * 32 : 0, (uint32_t*)pow_global, frame_memo && n_px > 0 ? 4 * VRT_PW_SLOTS : 0,
+                           (unsigned long long*)keys, n_keys);
+    }
+    if (n_px == 0) return VRT_OK;
+    for (int v0 = 0; v0 < n_views; v0 += 64) {
+        const int n = n_views - v0 < 64 ? n_views - v0 : 64;
+        for (int t = 0; t < 64; t++)
+            for (int a = 0; a < 4; a++)
+                org.o[t][a] = (keys && t < n && a < 3) ? (int32_t)(traversed[v0 + t].origin[a] / st->chunk_size) : 0;
+        hipLaunchKernelGGL(views_setup_kernel, dim3(1), dim3(64), 0, stream, d_cams, org, v0, n, view_tab);
+    }
+    TileGeom g;
+    g.pixels = d_pixels_xy;
+    g.n_px = n_px;
+    g.smax = smax;
+    const int resmode = res_mode(scene);
+    const bool big_scene = march_big_scene(scene);
+    P.g = g;
+    P.ray_seedidx = (const uint32_t*)((const char*)d_plan + 64 + align256(slots * 4));
+    P.ray_rgba = rgba;
+    P.rays = nullptr;
+    P.pow_global = pow_global;
+    P.first_draw = 1 + (st->dof != 0.0 ? 2 : 0);
+    P.per_pixel = ray_table_per_pixel(*st) ? 1 : 0;
+    P.lens = 0.0;
+    P.tab = ray_tab_at(const_cast<double*>(d_ray_table), slots);
+    P.views.view_tab = view_tab;
+    P.views.view_slots = (uint32_t)slots;
+    P.views.view_recip = slots > 1 ? (uint32_t)(((uint64_t)1 << 32) / (uint64_t)slots) : 0xffffffffu;
+    for (int64_t v0 = 0; v0 < n_views; v0 += w.per_launch) {
+        const int64_t nv = n_views - v0 < w.per_launch ? n_views - v0 : w.per_launch;
+        const int64_t n = nv * slots;
+        if (v0 != 0) clear_words(count, 256 + 8 * 128, stream);  // (first launch: frame_begin_kernel)
+        P.ray0 = v0 * slots;
+        P.views.view_first = (uint32_t)v0;
+        P.n = n;
+        P.chunk = march_chunk(n);
+        march_policy(big_scene, n, P.t_hit, P.t_end, P.max_iters);
+        P.list = nullptr;
+        P.list_count = nullptr;
+        P.list_seed = 0;
+        P.prefix_draws = 0;  // (lanes count per ray, as in march_kernel: nothing to take off again)
+        P.draws = d_draw_table;
+        P.n_draws = fast_draws;
+        P.draw_stride = fast_draws;
+        P.retrace_list = list;
+        P.retrace_count = count;
+        P.retrace_cap = (uint32_t)w.slow_cap;
+        P.queue_head = (unsigned long long*)(count + 2);
+        {
+            ProfScope ps(stream, VRT_PROF_MARCH);
+            launch_march_views<false>(P, march_grid(n), resmode, nv, stream);
+        }
+        // the two re-trace tiers of vrt_render_tile; their lists hold offsets in this launch, the view follows from them
+        ProfScope ps(stream, VRT_PROF_RETRACE);
+        P.list = list;
+        P.list_count = count;
+        P.draws = t_slow;
+        P.n_draws = D_SLOW;
+        P.draw_stride = VRT_SLOW_STRIDE;
+        P.list_cap = (uint32_t)w.slow_cap;
+        P.retrace_list = (uint32_t*)(ws + w.off_list_full);
+        P.retrace_count = count + 8;
+        P.retrace_cap = (uint32_t)w.full_cap;
+        P.queue_head = (unsigned long long*)(count + 4);
+        P.list_seed = 1;
+        launch_march_views<true>(P, 256, resmode, nv, stream);
+        P.list_seed = 2;
+        P.list = (uint32_t*)(ws + w.off_list_full);
+        P.list_count = count + 8;
+        P.draws = (double*)(ws + w.off_full);
+        P.n_draws = D_FULL_DEV;
+        P.draw_stride = D_FULL_DEV;
+        P.list_cap = (uint32_t)w.full_cap;
+        P.retrace_list = nullptr;
+        P.retrace_count = nullptr;
+        P.retrace_cap = 0;
+        P.queue_head = (unsigned long long*)(count + 10);
+        launch_march_views<true>(P, 64, resmode, nv, stream);
+    }
+    if (d_rgba_f32 || d_image_u8) {
+        ProfScope ps(stream, VRT_PROF_RESOLVE);
+        const int64_t tiles = (int64_t)((st->width + 15) / 16) * ((st->height + 15) / 16);
+        const int64_t rgrid = grid_for(n_px) > tiles ? grid_for(n_px) : tiles;
+        hipLaunchKernelGGL(resolve_views_kernel, dim3((unsigned)rgrid, (unsigned)(n_views < 65535 ? n_views : 65535)), dim3(VRT_BLOCK), 0, stream,
+                           *st, g, (const PlanHeader*)d_plan, (int)n_views, rgba, d_rgba_f32, d_image_u8);
     }
     HIP_TRY(hipGetLastError());
     return VRT_OK;
