@@ -296,6 +296,45 @@ int vrt_render_views(const vrt_scene* scene, const vrt_settings* st, const vrt_c
                      float* d_rgba_f32, uint8_t* d_image_u8, uint32_t* d_ray_rgba, vrt_ray* d_rays, uint64_t* d_stats,
                      const vrt_traversed* traversed, void* stream);
 
+/* ---- first hit ----------------------------------------------------------------------------------------
+ * What a pixel SEES: every primary ray of vrt_render_tile followed up to the moment `mat` is first non-empty (init.py:78)
+ * and no further -- depth maps, the voxel under the cursor, material-id images, line-of-sight queries.  The pass needs
+ * the cached ray table (lens quaternion and life per ray slot: the same jitter and the same life as the colour frame's
+ * ray), the camera, the chunk table and the voxel bytes; no draws, no materials, no workspace, no traversed list.
+ * One 48-byte record per ray. */
+typedef struct vrt_hit {
+    double  step;      /* ray.step when the loop of init.py:66 was left: at the first voxel, or >= life for a miss */
+    double  pos[3];    /* ray.pos at that moment */
+    int32_t cell[3];   /* floor(pos): the voxel asked for (init.py:76) */
+    int32_t material;  /* material id of the first voxel found (1..255), 0 = none within the ray's life, -1 = unused sample
+                          slot (every other field of such a record is 0) */
+} vrt_hit;
+
+/* d_hits[k], k = p * max_samples + s, describes ray slot k of vrt_render_tile for the same pixel list, settings and camera.
+ *   first_sample_only  nonzero: d_hits has n_px records, equal to records p * max_samples of the full call, and only those
+ *                      rays are marched.
+ *   d_ray_table        required (vrt_ray_table_build for these settings and cam->lens).
+ *   d_plan, n_distinct the plan of the pixel list, as vrt_render_tile takes them (checked, never read on the device).
+ *   d_stats            [VRT_NSTATS] uint64, zeroed by the callee: word 8 (VRT_S_RAYS) = rays traced, word 4 (VRT_C_HIT) =
+ *                      rays that found a voxel, every other word 0 (while the call runs the library keeps its launch-wide
+ *                      ray counter in the last word).
+ * The range rule is vrt_render_tile's and is checked before any HIP call; nothing is allocated or synchronised, so a call
+ * may be captured into a hipGraph. */
+int vrt_first_hit(const vrt_scene* scene, const vrt_settings* st, const vrt_camera* cam, const int32_t* d_pixels_xy,
+                  int64_t n_px, const void* d_plan, int64_t n_distinct, const double* d_ray_table,
+                  int32_t first_sample_only, vrt_hit* d_hits, uint64_t* d_stats, void* stream);
+
+/* vrt_first_hit for n_views cameras in one launch: d_cams as vrt_render_views takes them (a DEVICE array; equal lenses and
+ * the range rule are the caller's to check).  Records are view-major, [n_views][n_px * max_samples] (or [n_views][n_px]
+ * with first_sample_only); n_views * n_px * max_samples must stay below 2^32, and a batch of more than 2^28 ray slots is
+ * split into launches at view boundaries.  d_stats holds the batch's totals.  d_workspace: vrt_first_hit_views_workspace_bytes()
+ * bytes, for the view records only. */
+int vrt_first_hit_views_workspace_bytes(int32_t n_views, int64_t* bytes);
+int vrt_first_hit_views(const vrt_scene* scene, const vrt_settings* st, const vrt_camera* d_cams, int32_t n_views,
+                        const int32_t* d_pixels_xy, int64_t n_px, const void* d_plan, int64_t n_distinct,
+                        const double* d_ray_table, int32_t first_sample_only, void* d_workspace, int64_t workspace_bytes,
+                        vrt_hit* d_hits, uint64_t* d_stats, void* stream);
+
 /* Camera.trace (init.py:37-121) for explicit rays: direction (dir_x, dir_y), detail and the random draws the
  * ray may consume (d_draws[i * n_draws + k] = k-th random.random() of ray i).  d_rays[i].counters[VRT_C_DRAW]
  * tells how many were consumed.  Rays that would need more draws are counted in d_stats[VRT_S_RNG_EXHAUSTED].

@@ -91,6 +91,15 @@ RAY_FIELDS = [("x", "<i4"), ("y", "<i4"), ("s", "<i4"), ("color", "<i4", 3), ("a
               ("bounces", "<f8"), ("pos", "<f8", 3), ("vel", "<f8", 3)]
 RAY_BYTES = 152
 
+
+class VrtHit(C.Structure):
+    """vrt_hit (include/vrt.h): one first-hit record, 48 bytes."""
+    _fields_ = [("step", C.c_double), ("pos", C.c_double * 3), ("cell", C.c_int32 * 3), ("material", C.c_int32)]
+
+
+HIT_FIELDS = [("step", "<f8"), ("pos", "<f8", 3), ("cell", "<i4", 3), ("material", "<i4")]
+HIT_BYTES = 48
+
 _lib = None
 
 
@@ -135,6 +144,14 @@ def lib():
     L.vrt_render_views.restype = C.c_int
     L.vrt_render_views.argtypes = [C.POINTER(VrtScene), C.POINTER(VrtSettings), vp, i32, vp, i64, vp, i64, i32, vp, vp, vp, i64,
                                    vp, vp, vp, vp, vp, C.POINTER(VrtTraversed), vp]
+    L.vrt_first_hit.restype = C.c_int
+    L.vrt_first_hit.argtypes = [C.POINTER(VrtScene), C.POINTER(VrtSettings), C.POINTER(VrtCamera), vp, i64, vp, i64, vp, i32,
+                                vp, vp, vp]
+    L.vrt_first_hit_views_workspace_bytes.restype = C.c_int
+    L.vrt_first_hit_views_workspace_bytes.argtypes = [i32, C.POINTER(i64)]
+    L.vrt_first_hit_views.restype = C.c_int
+    L.vrt_first_hit_views.argtypes = [C.POINTER(VrtScene), C.POINTER(VrtSettings), vp, i32, vp, i64, vp, i64, vp, i32, vp, i64,
+                                      vp, vp, vp]
     L.vrt_draw_table_bytes.restype = C.c_int
     L.vrt_draw_table_bytes.argtypes = [i64, i32, C.POINTER(i64)]
     L.vrt_draw_table_build.restype = C.c_int
@@ -182,6 +199,7 @@ def lib():
 EXPORTS = ["vrt_abi_version", "vrt_status_string", "vrt_last_hip_error", "vrt_device_count", "vrt_release_caches", "vrt_voxel_offset",
            "vrt_max_samples", "vrt_plan_bytes", "vrt_plan_build", "vrt_workspace_bytes", "vrt_render_tile",
            "vrt_views_workspace_bytes", "vrt_render_views",
+           "vrt_first_hit", "vrt_first_hit_views_workspace_bytes", "vrt_first_hit_views",
            "vrt_draw_table_bytes", "vrt_draw_table_build", "vrt_ray_table_bytes", "vrt_ray_table_build",
            "vrt_pow_memo_create", "vrt_occupancy_build", "vrt_canvas_blit", "vrt_world_tables_bytes", "vrt_world_tables_build",
            "vrt_trace_workspace_bytes", "vrt_trace_rays", "vrt_rng_draws",

@@ -102,6 +102,60 @@ class RenderResult:
                 for a, b, c in zip(cx.tolist(), cy.tolist(), cz.tolist())]
 
 
+class HitResult:
+    """Device-side records of a first-hit pass (Camera.first_hit / first_hit_views): what every primary ray of the frame sees.
+    `step`, `pos`, `cell` and `material` are views of one buffer of 48-byte vrt_hit records (include/vrt.h), one per ray
+    slot p * max_samples + s (`samples` == max_samples) or one per pixel (`samples` == 1: every pixel's first sample)."""
+
+    def __init__(self, records, pixels, samples, max_samples, height, width, stats_dev):
+        import torch
+        n = records.numel() // nat.HIT_BYTES
+        f64 = records.view(torch.float64).view(n, nat.HIT_BYTES // 8)
+        i32 = records.view(torch.int32).view(n, nat.HIT_BYTES // 4)
+        self.records = records           # uint8 [n * 48]
+        self.step = f64[:, 0]            # float64 [n]: ray.step at the first voxel, or >= the ray's life for a miss
+        self.pos = f64[:, 1:4]           # float64 [n, 3]: ray.pos at that moment
+        self.cell = i32[:, 8:11]         # int32 [n, 3]: floor(pos)
+        self.material = i32[:, 11]       # int32 [n]: 1..255 the material found, 0 none, -1 unused sample slot
+        self.pixels = pixels             # numpy [n_px, 2] (x, y)
+        self.samples = samples
+        self.max_samples = max_samples
+        self.height, self.width = height, width
+        self._stats_dev = stats_dev
+        self._stats = None
+
+    @property
+    def stats(self):
+        """numpy int64[16], copied from the device on first use (a synchronisation): word 8 = rays traced, word 4 = rays that
+        found a voxel.  A batch's views share one block: the batch's totals."""
+        if self._stats is None:
+            self._stats = self._stats_dev.cpu().numpy()
+        return self._stats
+
+    def numpy(self):
+        """The records as a numpy structured array (fields step, pos, cell, material)."""
+        return self.records.cpu().numpy().view(np.dtype(nat.HIT_FIELDS))
+
+    def _scatter(self, values, fill, dtype):
+        import torch
+        img = torch.full((self.height, self.width), fill, dtype=dtype, device=self.records.device)
+        px = torch.from_numpy(self.pixels.astype(np.int64)).to(self.records.device)
+        img[px[:, 1], px[:, 0]] = values[:: self.samples]
+        return img
+
+    def depth_image(self):
+        """[height, width] float64: sample 0's step where it found a voxel, inf where it found none and at pixels that
+        are not listed."""
+        import torch
+        inf = torch.full_like(self.step, float("inf"))
+        return self._scatter(torch.where(self.material > 0, self.step, inf), float("inf"), torch.float64)
+
+    def material_image(self):
+        """[height, width] int32: the material id sample 0 found (0: none); -1 at pixels that are not listed."""
+        import torch
+        return self._scatter(self.material, -1, torch.int32)
+
+
 class Camera:
     def __init__(self, settings=None, device=None):
         import torch
@@ -766,6 +820,103 @@ class Camera:
                 res.stats = hstats
                 out.append(res)
         return out
+
+    # ------------------------------------------------------------------ first hit: what a pixel sees
+    def _first_hit_tables(self, dp, st):
+        """The plan and the ray table a first-hit pass reads (the lens jitter and the life of every ray are the static-seed
+        frame's).  Returns (ray table, retire): with cache_draws unset the tables were built for this call and `retire()`
+        drops them again once the pass has been launched."""
+        table = self._draw_table_for(dp, st, self.fast_draws)
+        self._order_after_table_builds(dp)   # (the ray table's build reads the draw table)
+        rtab = self._ray_table_for(dp, st, self.fast_draws, table)
+        self._order_after_table_builds(dp)
+
+        def retire():
+            if self.cache_draws:
+                return
+            for t in (dp.draw_table, dp.ray_table):
+                self._retire_table(dp, t)
+            dp.draw_table = dp.draw_key = dp.ray_table = dp.ray_key = None
+        return rtab, retire
+
+    def first_hit(self, thread=0, pixels=None, all_samples=False, stream=None):
+        """What every pixel of settings.pixels[thread] (or of an explicit pixel list) sees: the primary rays of render() --
+        the same lens jitter, the same life -- followed to their first voxel and no further (vrt_first_hit: no shading, no
+        draws, no traversed list).  Returns a HitResult of device tensors: one record per pixel (its first sample), or with
+        all_samples one per ray slot p * max_samples + s, unused sample slots marked material -1.  Nothing is copied to
+        the host and nothing synchronises; `stream` (a torch stream) defaults to the current one."""
+        torch = self._torch
+        L = nat.lib()
+        dev = self._require_device()
+        s = self._settings()
+        sc = self._ensure_scene()
+        st = self._c_settings(0)
+        with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            dp = self._plan_for(self._pixels_tensor(thread, pixels), st)
+            n_px = int(dp.array.shape[0])
+            cam = self._c_camera()
+            csc = self._c_scene(sc)
+            smax = L.vrt_max_samples(C.byref(st))
+            samples = smax if all_samples else 1
+            rtab, retire = self._first_hit_tables(dp, st)
+            records = torch.empty(max(n_px * samples, 1) * nat.HIT_BYTES, dtype=torch.uint8, device=dev)
+            stats = torch.empty(nat.NSTATS, dtype=torch.int64, device=dev)   # (the library clears it)
+            rc = L.vrt_first_hit(C.byref(csc), C.byref(st), C.byref(cam), dp.tensor.data_ptr(), n_px, dp.plan.data_ptr(),
+                                 dp.n_distinct, rtab.data_ptr(), 0 if all_samples else 1, records.data_ptr(), stats.data_ptr(),
+                                 torch.cuda.current_stream().cuda_stream)
+            retire()
+            nat.check(rc, "vrt_first_hit")
+        return HitResult(records[: n_px * samples * nat.HIT_BYTES], dp.array, samples, smax, int(s.height), int(s.width), stats)
+
+    def first_hit_views(self, poses, thread=0, pixels=None, all_samples=False, stream=None):
+        """first_hit() for many camera poses of one scene in one launch (vrt_first_hit_views): depth or material-id images
+        for stereo pairs, cube faces, a camera path, many agents.  poses: as render_views takes them; lens and settings are
+        the camera's own.  Returns one HitResult per view -- views into the batch's record buffer, bit-identical to first_hit()
+        at that pose; their `stats` is the batch's shared block.  Inside a stream capture the poses must be those of the
+        batch made just before it (their upload cannot be captured: render_views)."""
+        torch = self._torch
+        L = nat.lib()
+        s = self._settings()
+        rec = self._pose_records(poses, self.lens)
+        self._check_pose_range(rec, s)
+        n_views = int(rec.shape[0])
+        dev = self._require_device()
+        sc = self._ensure_scene()
+        st = self._c_settings(0)
+        with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            dp = self._plan_for(self._pixels_tensor(thread, pixels), st)
+            n_px = int(dp.array.shape[0])
+            csc = self._c_scene(sc)
+            smax = L.vrt_max_samples(C.byref(st))
+            if n_views * n_px * smax >= (1 << 32) - 1:
+                raise nat.VrtError("the batch is too large: views * pixels * samples must stay below 2**32 (%d * %d)"
+                                   % (n_views, n_px * smax))
+            samples = smax if all_samples else 1
+            ckey = rec.tobytes()
+            hit = getattr(self, "_views_cams", None)
+            if hit is not None and hit[0] == ckey:
+                cams = hit[1]
+            elif torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("first_hit_views() inside a stream capture needs the poses of the batch made just before "
+                                   "it (their upload cannot be captured)")
+            else:
+                cams = torch.from_numpy(rec).to(dev)
+                self._views_cams = (ckey, cams)
+            nb = C.c_int64(0)
+            nat.check(L.vrt_first_hit_views_workspace_bytes(n_views, C.byref(nb)), "vrt_first_hit_views_workspace_bytes")
+            ws = self._get_workspace(nb.value)
+            rtab, retire = self._first_hit_tables(dp, st)
+            per_view = n_px * samples * nat.HIT_BYTES
+            records = torch.empty(max(n_views * per_view, 1), dtype=torch.uint8, device=dev)
+            stats = torch.empty(nat.NSTATS, dtype=torch.int64, device=dev)   # (the library clears it)
+            rc = L.vrt_first_hit_views(C.byref(csc), C.byref(st), cams.data_ptr(), n_views, dp.tensor.data_ptr(), n_px,
+                                       dp.plan.data_ptr(), dp.n_distinct, rtab.data_ptr(), 0 if all_samples else 1,
+                                       ws.data_ptr(), ws.numel(), records.data_ptr(), stats.data_ptr(),
+                                       torch.cuda.current_stream().cuda_stream)
+            retire()
+            nat.check(rc, "vrt_first_hit_views")
+        return [HitResult(records[v * per_view:(v + 1) * per_view], dp.array, samples, smax, int(s.height), int(s.width), stats)
+                for v in range(n_views)]
 
     def tile(self, thread, t=0):
         """Reference signature and return triple (init.py:126-150): RGBA8 bytes of the full window (pixels of other

@@ -800,8 +800,11 @@ struct MarchParams {
     int32_t pool_keep;           // ... lanes that must still march for a pass to take another MARCH step at once
     int32_t list_seed;           // LIST: the lane that takes a listed ray seeds its draw row first (take_ray, SEED): 1 = the 113
                                  // draws that need no state twist, 2 = D_FULL_DEV draws from a full-state MT19937
-    int32_t prefix_draws;        // LIST: > 0 = the frame's march counted a re-traced ray's events up to the hit at which
+    union {
+        int32_t prefix_draws;    // LIST: > 0 = the frame's march counted a re-traced ray's events up to the hit at which
                                  // a row of this many draws ran out; the re-trace takes them off again (hit_body)
+        int32_t slot_stride;     // first_hit_kernel only: record k of the launch is ray slot ray0 + k * slot_stride (1, or the
+    };                           // sample slots per pixel when only every pixel's first sample is marched)
     int32_t ct_cells;            // > 0: the chunk table (that many cells) is copied to LDS
     int32_t ct_identity;         // the chunk table is (i + 1) | 1 << 24 (VRT_SCENE_TABLE_IS_IDENTITY): computed, not read
     int32_t trav_words;          // > 0: per-wave settled bitmaps of that many 32-bit words in LDS
@@ -817,7 +820,10 @@ struct MarchParams {
     const uint32_t* wt_table;    // ... the tables (vrt_scene.d_world_tables)
     // outputs
     uint32_t* ray_rgba;          // [rays of the tile] packed result (tile mode)
-    vrt_ray* rays;               // debug records (may be NULL)
+    union {
+        vrt_ray* rays;           // debug records (may be NULL)
+        vrt_hit* hits;           // first_hit_kernel only (which keeps no debug records): the launch's first-hit records
+    };
     uint64_t* stats;
     uint32_t* retrace_list;      // rays whose draws ran out are appended here (may be NULL)
     uint32_t* retrace_count;
@@ -1405,6 +1411,19 @@ __device__ __forceinline__ void resnap_commit_views(const PT& Q, const MarchCtx&
     r.resnaps++;
 }
 
+// The re-snap of the first-hit pass (first_hit_kernel only): it records no traversed list -- no keys, no bitmaps, no count of
+// re-snaps -- so only the chunk cursor moves.
+template <class PT>
+__device__ __forceinline__ void resnap_cursor(const PT& Q, const MarchCtx& C, Ray& r, int fx, int fy, int fz, int fl) {
+    const int ccx = fx >> Q.cs_shift, ccy = fy >> Q.cs_shift, ccz = fz >> Q.cs_shift;
+    r.nm4x = -(ccx << (Q.cs_shift + 2));
+    r.nm4y = -(ccy << (Q.cs_shift + 2));
+    r.nm4z = -(ccz << (Q.cs_shift + 2));
+    r.entry = chunk_entry_i(Q, C.ct, ccx - C.oc[0], ccy - C.oc[1], ccz - C.oc[2], C.dm[0], C.dm[1], C.dm[2], (fl & CF_CT_LDS) != 0,
+                            (fl & CF_CT_IDENTITY) != 0);
+    r.boff = ((r.entry & 0xffffffu) - 1u) << (3 * Q.cs_shift);
+}
+
 // `after`: a value that only exists once the caller's voxel reads are back.  The key passes through an empty statement that
 // names it, so the comparison (and the wait for the key) cannot be scheduled ahead of those reads
 template <bool BM, class PT>
@@ -1433,14 +1452,16 @@ __device__ __forceinline__ void resnap_finish(const PT& Q, const MarchCtx& C, co
 // SEED (re-trace launches): the draw row of a listed ray is seeded by the lane that takes the ray, here, instead of by a
 // launch of its own before the march (nobody else reads that row): 1 = the D_SLOW_DEV draws that need no state twist
 // (registers only), 2 = D_FULL_DEV draws from a full-state generator (a 624-word private array).
-template <bool RECORD, bool LIST, int PERPIX, bool SNAP = false, int SEED = 0>
+// FH (first_hit_kernel): the ray is followed to its first voxel only and needs no draws of its own -- the launch has no draw
+// table and no plan, and neither is read.
+template <bool RECORD, bool LIST, int PERPIX, bool SNAP = false, int SEED = 0, bool FH = false>
 __device__ __forceinline__ bool take_ray(const MarchParams& P, const MarchCtx& C, int64_t k, Ray& r, DgLane& dg, uint64_t wmin_key,
                                          SeenList<RECORD>& sl) {
     (void)dg; (void)wmin_key; (void)sl;
     const auto& Q = fresh_args(P);  // (see fresh_args)
     const int64_t off = LIST ? (int64_t)Q.list[k] : k;
     const int64_t ray = Q.ray0 + off;
-    const int64_t rowi = LIST ? k : ((C.tile && Q.ray_seedidx) ? (int64_t)Q.ray_seedidx[ray] : ray);
+    const int64_t rowi = LIST ? k : ((!FH && C.tile && Q.ray_seedidx) ? (int64_t)Q.ray_seedidx[ray] : ray);
     if (LIST && SEED != 0) {
         const int64_t p = ray / Q.g.smax;
         const uint64_t seed = ray_seed(Q.st, Q.g.smax, Q.g.pixels[2 * p], Q.g.pixels[2 * p + 1], (int)(ray - p * Q.g.smax));
@@ -1465,7 +1486,7 @@ __device__ __forceinline__ bool take_ray(const MarchParams& P, const MarchCtx& C
         ox = rec.ox; oy = rec.oy; oz = rec.oz; ow = rec.ow;
         life = (int)((uint32_t)ray - px * (uint32_t)Q.g.smax) < (int)rec.d0 ? rec.life : -1.0;
         t0 = t1 = t2 = 0.5;
-        if (life >= 0.0) {  // (an unused sample slot has no draw row: its index in the plan is 0xFFFFFFFF)
+        if (!FH && life >= 0.0) {  // (an unused sample slot has no draw row: its index in the plan is 0xFFFFFFFF)
             const double* row = Q.draws + rowi * Q.draw_stride + Q.first_draw;
             t0 = row[0];
             t1 = row[1];
@@ -1530,14 +1551,15 @@ __device__ __forceinline__ bool take_ray(const MarchParams& P, const MarchCtx& C
 // the re-trace list are the batch's and keep the batch offset (r.off).  The camera comes from the view's record (staged in
 // LDS for the first MarchParams::view_lds views, else from memory), not from the COLD_POS / COLD_ROT scalars.  Static seeds
 // and both cached tables are required (vrt_render_views), so P.per_pixel is 0 or 1 and every slot has a plan row.
-template <bool LIST, int SEED>
+// FH: see take_ray; PP: the ray table's layout -- 0 one record per ray slot, 1 per pixel, 2 ask P.per_pixel at run time
+template <bool LIST, int SEED, bool FH = false, int PP = 2>
 __device__ __forceinline__ bool take_ray_views(const MarchParams& P, const MarchCtx& C, int64_t k, Ray& r) {
     const auto& Q = fresh_args(P);  // (see fresh_args)
     const int64_t off = LIST ? (int64_t)Q.list[k] : k;
     const uint32_t bray = (uint32_t)(Q.ray0 + off);  // slot in the batch (< 2^32: vrt_render_views)
     const uint32_t v = bray / Q.views.view_slots;
     const uint32_t ray = bray - v * Q.views.view_slots;    // slot inside the view
-    const int64_t rowi = LIST ? k : (int64_t)Q.ray_seedidx[ray];
+    const int64_t rowi = LIST ? k : (FH ? 0 : (int64_t)Q.ray_seedidx[ray]);
     if (LIST && SEED != 0) {
         const uint32_t p = ray / (uint32_t)Q.g.smax;
         const uint64_t seed = ray_seed(Q.st, Q.g.smax, Q.g.pixels[2 * (int64_t)p], Q.g.pixels[2 * (int64_t)p + 1], (int)(ray - p * (uint32_t)Q.g.smax));
@@ -1547,14 +1569,14 @@ __device__ __forceinline__ bool take_ray_views(const MarchParams& P, const March
         __threadfence();  // (the row is read back below and by the ray's hits)
     }
     double life, ox, oy, oz, ow, t0, t1, t2;
-    if (Q.per_pixel) {
+    if (PP == 1 || (PP == 2 && Q.per_pixel)) {
         // the pixel's record (d0 = its sample count); the ray's first-hit draws come from the draw table
         const uint32_t px = ray / (uint32_t)Q.g.smax;
         const RayRecord rec = Q.tab.rec[px];
         ox = rec.ox; oy = rec.oy; oz = rec.oz; ow = rec.ow;
         life = (int)(ray - px * (uint32_t)Q.g.smax) < (int)rec.d0 ? rec.life : -1.0;
         t0 = t1 = t2 = 0.5;
-        if (life >= 0.0) {  // (an unused sample slot has no draw row: its index in the plan is 0xFFFFFFFF)
+        if (!FH && life >= 0.0) {  // (an unused sample slot has no draw row: its index in the plan is 0xFFFFFFFF)
             const double* row = Q.draws + rowi * Q.draw_stride + Q.first_draw;
             t0 = row[0];
             t1 = row[1];
@@ -1631,7 +1653,8 @@ __device__ __forceinline__ decltype(auto) march_args(const MarchParams& P) {
 // DEFER: the launch's traversed box has no settled bitmap -- the key reads of its re-snaps are compared after the voxel
 // reads have been issued (resnap_commit<DEFER>)
 // VIEWS: the launch's rays belong to several cameras (march_views_kernel; resnap_commit_views) -- 1: a ray's view is kept in
-// Ray::view, 2: it is worked out from the ray's slot (ray_view)
+// Ray::view, 2: it is worked out from the ray's slot (ray_view); 3: the first-hit pass, which records no traversed list at all
+// (first_hit_kernel; resnap_cursor)
 template <int SPEC, int RESMODE, bool RECORD, int LK, bool FRESH = VRT_FRESH_MARCH, int DEFER = 0, int VIEWS = 0>
 __device__ __forceinline__ void march_step(const MarchParams& P, const MarchCtx& C, Ray& r, int& state, int32_t (&cnt)[C_NLOCAL],
                                            uint64_t wmin_key, LkState& lk, SeenList<RECORD>& sl, DgLane& dg) {
@@ -1674,7 +1697,8 @@ __device__ __forceinline__ void march_step(const MarchParams& P, const MarchCtx&
             if (l4or == 0x80000000u) outside = !(r.px == 0.0 && r.py == 0.0 && r.pz == 0.0);
         }
         if (outside) {
-            if constexpr (VIEWS != 0) resnap_commit_views<VIEWS == 1>(Q, C, r, fx, fy, fz, fl);
+            if constexpr (VIEWS == 3) resnap_cursor(Q, C, r, fx, fy, fz, fl);
+            else if constexpr (VIEWS != 0) resnap_commit_views<VIEWS == 1>(Q, C, r, fx, fy, fz, fl);
             else resnap_commit<RECORD, FRESH, DEFER>(Q, C, r, fx, fy, fz, wmin_key, sl, fl, &pend);
             l4x = (int)(((unsigned)fx << 2) + (unsigned)r.nm4x);
             l4y = (int)(((unsigned)fy << 2) + (unsigned)r.nm4y);
@@ -2858,6 +2882,207 @@ __global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) march_views_ker
         }
     }
     march_epilogue<LIST>(P, S);
+}
+
+// ---- first_hit_kernel: what a pixel sees (vrt_first_hit, vrt_first_hit_views) -------------------------------------------
+// Every primary ray of a frame up to the moment `mat` is first non-empty (init.py:78) and no further: the lane takes a ray
+// (take_ray / take_ray_views: the cached record's lens quaternion and life, the camera), runs the shipped march_step until it
+// leaves LANE_MARCH, writes one vrt_hit and is idle again in the same pass.  There is one body, so there is nothing to wait
+// for and no t_hit / t_end: a pass marches until a lane is done, serves it, refills.  No colour, energy, bounces or draws,
+// no event counters, no seen list, no traversed keys (march_step<.., VIEWS = 3>: a re-snap only moves the chunk cursor), no
+// materials and no pow memo in LDS -- the static LDS is the offset tables and a few scalars; the dynamic LDS the chunk table
+// (if it fits) and, for a batch, the view records.
+// Record k of the launch goes to P.hits[k] and is ray slot P.ray0 + k * P.slot_stride (VIEWS: of the view k falls into).
+// PERPIX: the ray table holds one record per pixel; VIEWS: the launch's rays belong to several cameras.
+struct FirstHitShared {
+    uint32_t tab[3 * 256];
+    double cold[COLD_N];
+};
+__device__ __forceinline__ void write_hit(vrt_hit* h, double step, double px, double py, double pz, int cx, int cy, int cz, int material) {
+    // (8-byte stores: the record's alignment in the C ABI)
+    double* d = reinterpret_cast<double*>(h);
+    d[0] = step;
+    d[1] = px;
+    d[2] = py;
+    d[3] = pz;
+    int2* c = reinterpret_cast<int2*>(d + 4);
+    c[0] = make_int2(cx, cy);
+    c[1] = make_int2(cz, material);
+}
+template <int SPEC, int RESMODE, int PERPIX, bool VIEWS>
+__global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) first_hit_kernel(MarchParams P) {
+    static_assert(SPEC >= 4 && SPEC <= 16, "speculation depth");
+    static_assert(PERPIX == 0 || PERPIX == 1, "ray-table layout");
+    __shared__ FirstHitShared S;
+    extern __shared__ __align__(16) unsigned char s_dyn[];
+    MarchCtx C;
+    {
+        uint32_t* s_ct = reinterpret_cast<uint32_t*>(s_dyn);
+        for (int i = threadIdx.x; i < P.ct_cells; i += VRT_BLOCK) s_ct[i] = P.chunk_table[i];
+        for (int i = threadIdx.x; i < 256; i += VRT_BLOCK) {
+            const int c = i < P.cs ? i : 0;  // (entries beyond the chunk are never selected)
+            S.tab[i] = (uint32_t)voxel_offset(P.cs, c, 0, 0);
+            S.tab[256 + i] = (uint32_t)voxel_offset(P.cs, 0, c, 0);
+            S.tab[512 + i] = (uint32_t)voxel_offset(P.cs, 0, 0, c);
+        }
+        if (threadIdx.x == 0) {
+            for (int j = 0; j < COLD_N; j++) S.cold[j] = 0.0;
+            if (!VIEWS) {  // (a batch has no one camera: MarchParams::views lies where cam does)
+                for (int a = 0; a < 3; a++) S.cold[COLD_POS + a] = P.cam.pos[a];
+                for (int a = 0; a < 4; a++) S.cold[COLD_ROT + a] = P.cam.rot[a];
+            }
+            S.cold[COLD_DIST_MIN] = P.st.dist_min;
+            S.cold[COLD_CS] = (double)P.cs;
+            S.cold[COLD_INV_CS] = 1.0 / (double)P.cs;
+        }
+        C.vw = nullptr;
+        if (VIEWS) {
+            double* s_views = reinterpret_cast<double*>(s_dyn + P.views.view_lds_off);
+            const double* first = P.views.view_tab + (int64_t)P.views.view_first * VRT_VIEW_WORDS;
+            for (int i = threadIdx.x; i < P.views.view_lds * VRT_VIEW_WORDS; i += VRT_BLOCK) s_views[i] = first[i];
+            C.vw = (const lds_char*)s_views;
+        }
+        C.tab = (const lds_char*)S.tab;
+        C.tl[0] = 0;
+        C.tl[1] = 1024;
+        C.tl[2] = 2048;
+        C.ct = (const lds_u32*)s_ct;
+        C.bm = nullptr;
+        C.mats = nullptr;
+        C.cold = (const lds_f64*)S.cold;
+        C.tot = nullptr;
+        C.pc.keys = C.pc.vals = C.pc.gkeys = C.pc.gvals = nullptr;
+        C.vox = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(P.voxels), 0, (int)P.vox_bytes, 0x00020000);
+        C.cs4 = (unsigned)P.cs << 2;
+        C.cs = (double)P.cs;
+        C.inv_cs = 1.0 / C.cs;
+        C.kept_cs = true;
+        C.has_bm = false;
+        C.tile = true;
+        C.wt = nullptr;
+        C.cs3 = 1u << (3 * P.cs_shift);
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            C.td[a] = C.toc[a] = C.wb[a] = 0;
+            C.oc[a] = P.origin_c[a];
+            C.dm[a] = P.dims[a];
+        }
+    }
+    __syncthreads();
+
+    // the hand-out loop of march_kernel: `chunk` consecutive records per wave from a launch-wide counter
+    const int64_t count = P.n;
+    const int64_t chunk = P.chunk;
+    const uint32_t stride = (uint32_t)P.slot_stride;
+    // VIEWS: records per view (the view's slots, or its pixels when only first samples are marched)
+    const uint32_t view_recs = VIEWS ? P.views.view_slots / stride : 1u;
+    int64_t next = 0, range_end = 0;
+    bool more = true;
+    if (chunk == 0) {  // static contiguous range per wave
+        const int64_t n_waves = (int64_t)gridDim.x * (VRT_BLOCK / VRT_WAVE);
+        const int64_t wave = (int64_t)blockIdx.x * (VRT_BLOCK / VRT_WAVE) + (threadIdx.x >> 6);
+        int64_t per = (count + n_waves - 1) / n_waves;
+        per = (per + 7) & ~(int64_t)7;
+        next = wave * per;
+        range_end = next + per < count ? next + per : count;
+        more = false;
+    }
+
+    Ray r;
+    r.px = r.py = r.pz = r.vx = r.vy = r.vz = 0;
+    r.step = r.life = r.bounces = r.energy = 0;
+    r.nm4x = r.nm4y = r.nm4z = 0;
+    r.entry = 0;
+    r.boff = 0;
+    r.color = 0;
+    r.ndraw = r.resnaps = 0;
+    r.off = 0;
+    r.rowi = 0;
+    r.d0 = r.d1 = r.d2 = 0.5;
+    r.view = 0;
+    uint32_t rec = 0;        // the record the lane's ray is written to
+    int state = LANE_IDLE;
+    uint32_t n_rays = 0, n_found = 0;  // wave-uniform: rays traced / rays that found a voxel
+    // what the shared bodies take besides the ray and the pass has no use for (all of it dead code here)
+    int32_t cnt[C_NLOCAL];
+#pragma unroll
+    for (int j = 0; j < C_NLOCAL; j++) cnt[j] = 0;
+    SeenList<false> sl;
+    sl.n = 0;
+    LkState lk;
+    lk.okey = ~0u;
+    lk.oword = 0;
+    lk.brick_slot = nullptr;
+    DgLane dg;
+#ifdef VRT_DIAG
+    __shared__ unsigned long long s_dg[VRT_BLOCK / VRT_WAVE][DG_N];  // (the bodies count into it; this pass reports nothing)
+    dg.acc = (__attribute__((address_space(3))) unsigned long long*)&s_dg[threadIdx.x >> 6][0];
+    if ((threadIdx.x & 63) == 0)
+        for (int j = 0; j < DG_N; j++) dg.acc[j] = 0;
+    dg.brick = ~0u;
+    dg.bv = 0;
+#endif
+
+    for (;;) {
+        // ------------------------------------------------------------------ refill idle lanes
+        unsigned long long idle_mask = __ballot(state == LANE_IDLE);
+        while (idle_mask != 0ull && (next < range_end || more)) {
+            if (next >= range_end) {  // take the next chunk (one atomic per wave per chunk)
+                unsigned long long base = 0;
+                if ((threadIdx.x & 63) == 0) base = atomicAdd(P.queue_head, (unsigned long long)chunk);
+                base = wave_first_u64(base);
+                if ((int64_t)base >= count) {
+                    more = false;
+                    break;
+                }
+                next = (int64_t)base;
+                range_end = next + chunk < count ? next + chunk : count;
+            }
+            const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(idle_mask >> 32),
+                                                            __builtin_amdgcn_mbcnt_lo((unsigned)idle_mask, 0u));
+            const int64_t k = next + rank;
+            next += __popcll(idle_mask);
+            if (state == LANE_IDLE && k < range_end) {
+                rec = (uint32_t)k;
+                // the record's ray slot, as an offset in the launch
+                uint32_t slot = rec;
+                if (stride != 1u) {
+                    if (VIEWS) {
+                        const uint32_t v = rec / view_recs;
+                        slot = v * P.views.view_slots + (rec - v * view_recs) * stride;
+                    } else {
+                        slot = rec * stride;
+                    }
+                }
+                bool taken;
+                if constexpr (VIEWS) taken = take_ray_views<false, 0, true, PERPIX>(P, C, (int64_t)slot, r);
+                else taken = take_ray<false, false, PERPIX, false, 0, true>(P, C, (int64_t)slot, r, dg, 0ull, sl);
+                if (taken) state = LANE_MARCH;
+                else write_hit(fresh_args(P).hits + rec, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, -1);  // unused sample slot
+            }
+            idle_mask = __ballot(state == LANE_IDLE);
+        }
+        if (__ballot(state != LANE_IDLE) == 0ull) break;  // range exhausted and every lane finished
+
+        // ------------------------------------------------------------------ MARCH steps, until a lane is done
+        while (__ballot(state > LANE_MARCH) == 0ull) {
+            if (state == LANE_MARCH) march_step<SPEC, RESMODE, false, 0, VRT_FRESH_MARCH, 0, 3>(P, C, r, state, cnt, 0ull, lk, sl, dg);
+        }
+
+        // ------------------------------------------------------------------ the record (LANE_HIT: the first voxel; LANE_ENDED: none)
+        n_rays += (uint32_t)__popcll(__ballot(state > LANE_MARCH));
+        n_found += (uint32_t)__popcll(__ballot(state == LANE_HIT));
+        if (state > LANE_MARCH) {
+            int cx, cy, cz;
+            floor3_i32(r.px, r.py, r.pz, cx, cy, cz);
+            write_hit(fresh_args(P).hits + rec, r.step, r.px, r.py, r.pz, cx, cy, cz, state == LANE_HIT ? (int)(r.color >> 24) : 0);
+            state = LANE_IDLE;
+        }
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (n_rays) atomicAdd((unsigned long long*)&P.stats[VRT_S_RAYS], (unsigned long long)n_rays);
+        if (n_found) atomicAdd((unsigned long long*)&P.stats[VRT_C_HIT], (unsigned long long)n_found);
+    }
 }
 
 // ---- march_pool_kernel: the same bodies, rays regrouped between the lanes of a wave through LDS ------------------------
@@ -4828,6 +5053,158 @@ int vrt_render_views(const vrt_scene* scene, const vrt_settings* st, const vrt_c
         const int64_t rgrid = grid_for(n_px) > tiles ? grid_for(n_px) : tiles;
         hipLaunchKernelGGL(resolve_views_kernel, dim3((unsigned)rgrid, (unsigned)(n_views < 65535 ? n_views : 65535)), dim3(VRT_BLOCK), 0, stream,
                            *st, g, (const PlanHeader*)d_plan, (int)n_views, rgba, d_rgba_f32, d_image_u8);
+    }
+    HIP_TRY(hipGetLastError());
+    return VRT_OK;
+}
+
+// ---- first hit (vrt_first_hit, vrt_first_hit_views) ----------------------------------------------------------------------
+}  // extern "C"
+
+// dynamic LDS of a first-hit launch: the chunk table (if it fits) | the view records that fit (n_views: of this launch; 0: one camera)
+static inline size_t first_hit_lds(MarchParams& P, int64_t n_views) {
+    P.snap_flags = (P.ct_cells != 0 ? CF_CT_LDS : 0) | (P.ct_identity != 0 ? CF_CT_IDENTITY : 0);
+    size_t n = ((size_t)P.ct_cells * 4 + 15) & ~(size_t)15;
+    if (n_views > 0) {
+        const int64_t fit = n_views < VRT_VIEWS_LDS_MAX ? n_views : VRT_VIEWS_LDS_MAX;
+        P.views.view_lds = (int32_t)fit;
+        P.views.view_lds_off = (int32_t)n;
+        n += (size_t)fit * VRT_VIEW_WORDS * 8;
+    }
+    return n + 16;
+}
+// kernel variant: resolution mode from vrt_scene.max_resolution (8 positions per step for resolutions <= 2, VRT_SPEC for the
+// generic instance, like the frame's march of scenes that fit the caches), ray-table layout, one camera or several
+template <bool VIEWS>
+static void launch_first_hit(MarchParams P, int grid, int resmode, int64_t n_views, hipStream_t stream) {
+    const size_t lds = first_hit_lds(P, VIEWS ? n_views : 0);
+#define VRT_LAUNCH_FH(SPEC_, RES_)                                                                                           \
+    do {                                                                                                                     \
+        if (P.per_pixel)                                                                                                     \
+            hipLaunchKernelGGL((first_hit_kernel<SPEC_, RES_, 1, VIEWS>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);        \
+        else                                                                                                                 \
+            hipLaunchKernelGGL((first_hit_kernel<SPEC_, RES_, 0, VIEWS>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);        \
+    } while (0)
+    if (resmode == 0) VRT_LAUNCH_FH(VRT_SPEC_DEEP, 0);
+    else if (resmode == 1) VRT_LAUNCH_FH(VRT_SPEC_DEEP, 1);
+    else VRT_LAUNCH_FH(VRT_SPEC, 2);
+#undef VRT_LAUNCH_FH
+}
+// what both entry points check and set after fill_params: the pass reads no plan, draw table, materials or keys
+static int first_hit_params(MarchParams& P, const vrt_settings* st, const int32_t* d_pixels_xy, int64_t n_px, const void* d_plan,
+                            int64_t n_distinct, const double* d_ray_table, vrt_hit* d_hits, int64_t n_views) {
+    if (n_px < 0 || (n_px > 0 && !d_pixels_xy) || !d_plan || !d_ray_table || !d_hits) return VRT_ERR_ARG;
+    if (!plan_supported(st) || st->seed_nonce != 0) return VRT_ERR_ARG;  // (the ray table is a static-seed run's)
+    const int smax = vrt_max_samples(st);
+    const int64_t slots = n_px * smax;
+    if (n_views * slots >= 4294967295ll) return VRT_ERR_ARG;
+    if (n_distinct < 0 || n_distinct > slots) return VRT_ERR_ARG;
+    P.g.pixels = d_pixels_xy;
+    P.g.n_px = n_px;
+    P.g.smax = smax;
+    P.per_pixel = ray_table_per_pixel(*st) ? 1 : 0;
+    P.tab = ray_tab_at(const_cast<double*>(d_ray_table), slots);
+    return VRT_OK;
+}
+
+extern "C" {
+
+int vrt_first_hit(const vrt_scene* scene, const vrt_settings* st, const vrt_camera* cam, const int32_t* d_pixels_xy, int64_t n_px,
+                  const void* d_plan, int64_t n_distinct, const double* d_ray_table, int32_t first_sample_only, vrt_hit* d_hits,
+                  uint64_t* d_stats, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    MarchParams P;
+    int rc = fill_params(P, scene, st, cam, nullptr, d_stats);  // (the range rule of a frame, before any HIP call)
+    if (rc != VRT_OK) return rc;
+    rc = first_hit_params(P, st, d_pixels_xy, n_px, d_plan, n_distinct, d_ray_table, d_hits, 1);
+    if (rc != VRT_OK) return rc;
+    frame_begin(d_stats, nullptr, 0, nullptr, 0, nullptr, stream);
+    if (n_px == 0) return VRT_OK;
+    const int64_t stride = first_sample_only ? P.g.smax : 1;
+    const int64_t records = first_sample_only ? n_px : n_px * P.g.smax;
+    int64_t per_launch = batch_rays() / stride;
+    if (per_launch < 1) per_launch = 1;
+    const int resmode = res_mode(scene);
+    P.slot_stride = (int32_t)stride;
+    // the launch-wide record counter: the statistics' last word, which this pass reports as 0 -- cleared with the statistics
+    // before the first launch and again behind every launch (nothing is allocated here, and there is no workspace)
+    P.queue_head = (unsigned long long*)(d_stats + VRT_NSTATS - 1);
+    for (int64_t r0 = 0; r0 < records; r0 += per_launch) {
+        const int64_t n = records - r0 < per_launch ? records - r0 : per_launch;
+        P.ray0 = r0 * stride;
+        P.n = n;
+        P.chunk = march_chunk(n);
+        P.hits = d_hits + r0;
+        {
+            ProfScope ps(stream, VRT_PROF_MARCH);
+            launch_first_hit<false>(P, march_grid(n), resmode, 0, stream);
+        }
+        clear_words(d_stats + VRT_NSTATS - 1, 8, stream);
+    }
+    HIP_TRY(hipGetLastError());
+    return VRT_OK;
+}
+
+int vrt_first_hit_views_workspace_bytes(int32_t n_views, int64_t* bytes) {
+    if (n_views < 1 || !bytes) return VRT_ERR_ARG;
+    *bytes = align256((int64_t)n_views * VRT_VIEW_WORDS * 8);
+    return VRT_OK;
+}
+
+int vrt_first_hit_views(const vrt_scene* scene, const vrt_settings* st, const vrt_camera* d_cams, int32_t n_views,
+                        const int32_t* d_pixels_xy, int64_t n_px, const void* d_plan, int64_t n_distinct, const double* d_ray_table,
+                        int32_t first_sample_only, void* d_workspace, int64_t workspace_bytes, vrt_hit* d_hits, uint64_t* d_stats,
+                        void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!d_cams || n_views < 1) return VRT_ERR_ARG;
+    // the scene and settings checks of a frame; the cameras are on the device (their range is the caller's to check: see
+    // vrt_render_views)
+    vrt_camera cam0;
+    for (int a = 0; a < 3; a++) cam0.pos[a] = 0.0;
+    cam0.rot[0] = cam0.rot[1] = cam0.rot[2] = 0.0;
+    cam0.rot[3] = 1.0;
+    cam0.lens = 0.0;
+    MarchParams P;
+    int rc = fill_params(P, scene, st, &cam0, nullptr, d_stats);
+    if (rc != VRT_OK) return rc;
+    rc = first_hit_params(P, st, d_pixels_xy, n_px, d_plan, n_distinct, d_ray_table, d_hits, n_views);
+    if (rc != VRT_OK) return rc;
+    if (!d_workspace) return VRT_ERR_ARG;
+    if (workspace_bytes < align256((int64_t)n_views * VRT_VIEW_WORDS * 8)) return VRT_ERR_WORKSPACE;
+    double* view_tab = (double*)d_workspace;
+    frame_begin(d_stats, nullptr, 0, nullptr, 0, nullptr, stream);
+    if (n_px == 0) return VRT_OK;
+    ViewOrigins org;  // (no traversed boxes: the origins of the records stay 0)
+    for (int t = 0; t < 64; t++)
+        for (int a = 0; a < 4; a++) org.o[t][a] = 0;
+    for (int v0 = 0; v0 < n_views; v0 += 64)
+        hipLaunchKernelGGL(views_setup_kernel, dim3(1), dim3(64), 0, stream, d_cams, org, v0, n_views - v0 < 64 ? n_views - v0 : 64, view_tab);
+    const int64_t slots = n_px * P.g.smax;
+    const int64_t stride = first_sample_only ? P.g.smax : 1;
+    const int64_t view_recs = first_sample_only ? n_px : slots;
+    // launches end at view boundaries: as many whole views as fit batch_rays() slots, at least one
+    int64_t per_launch = batch_rays() / slots;
+    if (per_launch < 1) per_launch = 1;
+    const int resmode = res_mode(scene);
+    P.slot_stride = (int32_t)stride;
+    P.queue_head = (unsigned long long*)(d_stats + VRT_NSTATS - 1);  // (see vrt_first_hit)
+    P.views.view_tab = view_tab;
+    P.views.view_cells = 0;
+    P.views.view_slots = (uint32_t)slots;
+    P.views.view_recip = 0;
+    for (int64_t v0 = 0; v0 < n_views; v0 += per_launch) {
+        const int64_t nv = n_views - v0 < per_launch ? n_views - v0 : per_launch;
+        const int64_t n = nv * view_recs;
+        P.ray0 = v0 * slots;
+        P.views.view_first = (uint32_t)v0;
+        P.n = n;
+        P.chunk = march_chunk(n);
+        P.hits = d_hits + v0 * view_recs;
+        {
+            ProfScope ps(stream, VRT_PROF_MARCH);
+            launch_first_hit<true>(P, march_grid(n), resmode, nv, stream);
+        }
+        clear_words(d_stats + VRT_NSTATS - 1, 8, stream);
     }
     HIP_TRY(hipGetLastError());
     return VRT_OK;
