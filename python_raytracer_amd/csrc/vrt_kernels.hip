@@ -1438,6 +1438,16 @@ __device__ __forceinline__ void resnap_finish(const PT& Q, const MarchCtx& C, co
     }
 }
 
+// SEED: the lane that takes a listed ray seeds its draw row (pixel x, y, sample s of the frame or of the view)
+template <int SEED, class Args>
+__device__ __forceinline__ void seed_row(const Args& Q, int x, int y, int s, int64_t rowi) {
+    const uint64_t seed = ray_seed(Q.st, Q.g.smax, x, y, s);
+    double* row = const_cast<double*>(Q.draws) + rowi * Q.draw_stride;
+    if (SEED == 1) mt_seed_draws<true>(seed, D_SLOW_DEV, row);
+    else mt_full_draws(seed, D_FULL_DEV, row);
+    __threadfence();  // (the row is read back below and by the ray's hits)
+}
+
 // IDLE -> MARCH: the lane takes ray k of the launch (init.py:41-59 with the lens quaternion and the life from the ray
 // table).  False for an unused sample slot of the tile.
 // PERPIX: the ray table holds one record per pixel (ray_table_per_pixel) -- 0 no, 1 yes, 2 ask P.per_pixel at run time
@@ -1464,11 +1474,7 @@ __device__ __forceinline__ bool take_ray(const MarchParams& P, const MarchCtx& C
     const int64_t rowi = LIST ? k : ((!FH && C.tile && Q.ray_seedidx) ? (int64_t)Q.ray_seedidx[ray] : ray);
     if (LIST && SEED != 0) {
         const int64_t p = ray / Q.g.smax;
-        const uint64_t seed = ray_seed(Q.st, Q.g.smax, Q.g.pixels[2 * p], Q.g.pixels[2 * p + 1], (int)(ray - p * Q.g.smax));
-        double* row = const_cast<double*>(Q.draws) + rowi * Q.draw_stride;
-        if (SEED == 1) mt_seed_draws<true>(seed, D_SLOW_DEV, row);
-        else mt_full_draws(seed, D_FULL_DEV, row);
-        __threadfence();  // (the row is read back below and by the ray's hits)
+        seed_row<SEED>(Q, Q.g.pixels[2 * p], Q.g.pixels[2 * p + 1], (int)(ray - p * Q.g.smax), rowi);
     }
     double life, ox, oy, oz, ow, t0, t1, t2;
     if (PERPIX == 3 || (PERPIX == 4 && Q.per_pixel == 2)) {
@@ -1552,6 +1558,10 @@ __device__ __forceinline__ bool take_ray(const MarchParams& P, const MarchCtx& C
 // LDS for the first MarchParams::view_lds views, else from memory), not from the COLD_POS / COLD_ROT scalars.  Static seeds
 // and both cached tables are required (vrt_render_views), so P.per_pixel is 0 or 1 and every slot has a plan row.
 // FH: see take_ray; PP: the ray table's layout -- 0 one record per ray slot, 1 per pixel, 2 ask P.per_pixel at run time
+// (seed_row is take_ray's.  The record fetch and the tail from camera_forward on are written out in both: the fetch as one
+// function keeps every register figure but changes the instruction streams of the frame kernels that read per-pixel
+// records; the tail as one function takes a vector register off eight march_kernel / march_pool_kernel instances --
+// 112 -> 111 for march_kernel<8,0,false,false,0,0> -- and the frame kernels are pinned.)
 template <bool LIST, int SEED, bool FH = false, int PP = 2>
 __device__ __forceinline__ bool take_ray_views(const MarchParams& P, const MarchCtx& C, int64_t k, Ray& r) {
     const auto& Q = fresh_args(P);  // (see fresh_args)
@@ -1562,11 +1572,7 @@ __device__ __forceinline__ bool take_ray_views(const MarchParams& P, const March
     const int64_t rowi = LIST ? k : (FH ? 0 : (int64_t)Q.ray_seedidx[ray]);
     if (LIST && SEED != 0) {
         const uint32_t p = ray / (uint32_t)Q.g.smax;
-        const uint64_t seed = ray_seed(Q.st, Q.g.smax, Q.g.pixels[2 * (int64_t)p], Q.g.pixels[2 * (int64_t)p + 1], (int)(ray - p * (uint32_t)Q.g.smax));
-        double* row = const_cast<double*>(Q.draws) + rowi * Q.draw_stride;
-        if (SEED == 1) mt_seed_draws<true>(seed, D_SLOW_DEV, row);
-        else mt_full_draws(seed, D_FULL_DEV, row);
-        __threadfence();  // (the row is read back below and by the ray's hits)
+        seed_row<SEED>(Q, Q.g.pixels[2 * (int64_t)p], Q.g.pixels[2 * (int64_t)p + 1], (int)(ray - p * (uint32_t)Q.g.smax), rowi);
     }
     double life, ox, oy, oz, ow, t0, t1, t2;
     if (PP == 1 || (PP == 2 && Q.per_pixel)) {
@@ -2551,6 +2557,101 @@ __device__ __forceinline__ void diag_flush(DgLane& dg, unsigned long long dg_sta
 }
 #endif
 
+// ---- what the persistent kernels share (march_kernel, march_views_kernel, first_hit_kernel, march_pool_kernel) ----------
+// The hand-out: rays are handed out in chunks of `chunk` consecutive rays from a launch-wide counter (P.queue_head) --
+// coherent lanes, balanced waves -- or, with chunk == 0, as one static contiguous range per wave.  Every member is
+// wave-uniform.  A kernel's refill loop reads
+//     while (idle_mask != 0 && H.left()) { if (H.used_up()) { H.take_chunk(..); if (!H.more) break; }  k = H.hand(idle_mask);  <take ray k> }
+struct HandOut {
+    int64_t count, chunk, next, range_end;
+    bool more;  // the launch-wide counter may still have rays
+    __device__ __forceinline__ void init(int64_t count_, int64_t chunk_) {
+        count = count_;
+        chunk = chunk_;
+        next = range_end = 0;
+        more = true;
+        if (chunk == 0) {  // static contiguous range per wave
+            const int64_t n_waves = (int64_t)gridDim.x * (VRT_BLOCK / VRT_WAVE);
+            const int64_t wave = (int64_t)blockIdx.x * (VRT_BLOCK / VRT_WAVE) + (threadIdx.x >> 6);
+            int64_t per = (count + n_waves - 1) / n_waves;
+            per = (per + 7) & ~(int64_t)7;
+            next = wave * per;
+            range_end = next + per < count ? next + per : count;
+            more = false;
+        }
+    }
+    __device__ __forceinline__ bool left() const { return next < range_end || more; }
+    __device__ __forceinline__ bool used_up() const { return next >= range_end; }
+    // the next chunk of the launch-wide counter (one atomic per wave per chunk); `more` is false after it if the counter
+    // has run dry.  (The caller tests `more` itself: with the test folded into a returned bool, march_views_kernel<4,2,true,2>
+    // spills 6 vector registers, not 2.)
+    __device__ __forceinline__ void take_chunk(unsigned long long* queue_head) {
+        unsigned long long base = 0;
+        if ((threadIdx.x & 63) == 0) base = atomicAdd(queue_head, (unsigned long long)chunk);
+        base = wave_first_u64(base);  // (into scalar registers: what is derived from it stays wave-uniform, scalar code)
+        if ((int64_t)base >= count) {
+            more = false;
+            return;
+        }
+        next = (int64_t)base;
+        range_end = next + chunk < count ? next + chunk : count;
+    }
+    // the ray this lane may take -- the idle lanes take consecutive ones -- if it lies below range_end
+    __device__ __forceinline__ int64_t hand(unsigned long long idle_mask) {
+        const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(idle_mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)idle_mask, 0u));
+        const int64_t k = next + rank;
+        next += __popcll(idle_mask);
+        return k;
+    }
+};
+// a lane without a ray
+__device__ __forceinline__ void ray_clear(Ray& r) {
+    r.px = r.py = r.pz = r.vx = r.vy = r.vz = 0;
+    r.step = r.life = r.bounces = r.energy = 0;
+    r.nm4x = r.nm4y = r.nm4z = 0;
+    r.entry = 0;
+    r.boff = 0;
+    r.color = 0;
+    r.ndraw = r.resnaps = 0;
+    r.off = 0;
+    r.rowi = 0;
+    r.d0 = r.d1 = r.d2 = 0.5;
+    r.view = 0;
+}
+// what the shared bodies take and only the lookup variants / the record-keeping kernels use (march_kernel adds its own)
+__device__ __forceinline__ LkState lk_unused() {
+    LkState lk;
+    lk.okey = ~0u;
+    lk.oword = 0;
+    lk.brick_slot = nullptr;
+    return lk;
+}
+__device__ __forceinline__ SeenList<false> seen_unused() {
+    SeenList<false> sl;
+    sl.n = 0;
+    return sl;
+}
+// the diagnostic build's per-wave sums (the bodies count into them in every kernel; only the frame kernels report them)
+#ifdef VRT_DIAG
+#define DG_LANE(dg)                                                                                   \
+    DgLane dg;                                                                                        \
+    __shared__ unsigned long long s_dg[VRT_BLOCK / VRT_WAVE][DG_N];                                   \
+    dg.acc = (__attribute__((address_space(3))) unsigned long long*)&s_dg[threadIdx.x >> 6][0];       \
+    if ((threadIdx.x & 63) == 0)                                                                      \
+        for (int j = 0; j < DG_N; j++) dg.acc[j] = 0;                                                 \
+    dg.brick = ~0u;                                                                                   \
+    dg.bv = 0
+#else
+#define DG_LANE(dg) DgLane dg
+#endif
+// the view records of a batched launch that fit into LDS (MarchParams::view_lds of them, from view_first on) -> C.vw
+__device__ __forceinline__ void stage_views(const MarchParams& P, unsigned char* s_dyn, MarchCtx& C) {
+    double* s_views = reinterpret_cast<double*>(s_dyn + P.views.view_lds_off);
+    const double* first = P.views.view_tab + (int64_t)P.views.view_first * VRT_VIEW_WORDS;
+    for (int i = threadIdx.x; i < P.views.view_lds * VRT_VIEW_WORDS; i += VRT_BLOCK) s_views[i] = first[i];
+    C.vw = (const lds_char*)s_views;
+}
+
 // Persistent waves, one ray per lane.  Every lane is a small state machine: MARCH (phase A of the reference loop: snap
 // chunk, look up the voxel, advance -- init.py:66-77, 114-116), HIT (phase B: shade, test termination, reflect, advance
 // -- init.py:78-116), ENDED (background + outputs -- init.py:119-120, 141-142), IDLE (take the next ray of the wave's
@@ -2574,8 +2675,10 @@ __device__ __forceinline__ void diag_flush(DgLane& dg, unsigned long long dg_sta
 // 1 and 2 are kept for measurement (VRT_LOOKUP=1|2, profiles/r02_v7_lookup_variants.md); a hit reads the byte in both.
 // W: the scene's blocks lie in table order and the march step looks ahead across chunk borders (march_step_w)
 // DEFER: see march_step
-// (march_views_kernel below repeats this kernel's refill / march / hit / ended loop for batched launches, so that this
-// kernel's code generation stays as it is: a fix to the hand-out loop belongs in both.)
+// (The lane set-up is shared with the other persistent kernels: ray_clear, lk_unused, seen_unused, DG_LANE above.  The hand-out
+// is HandOut's, written out: with the struct the instances that make their own ray records (PERPIX 3) need 2 more vector
+// registers and every march_pool_kernel instance spills 1-2 more scalar registers.  A fix to HandOut belongs here and in
+// march_pool_kernel's refill too; march_views_kernel and first_hit_kernel use the struct.)
 template <int SPEC, int RESMODE, bool RECORD, bool LIST, int LK = 0, int PERPIX = (RECORD || LIST) ? 4 : 0, bool W = false, bool DEFER = false, int SEED = 0>
 __global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) march_kernel(MarchParams P) {
     static_assert(SPEC >= 4 && SPEC <= 16, "speculation depth");
@@ -2606,16 +2709,7 @@ __global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) march_kernel(Ma
     }
 
     Ray r;
-    r.px = r.py = r.pz = r.vx = r.vy = r.vz = 0;
-    r.step = r.life = r.bounces = r.energy = 0;
-    r.nm4x = r.nm4y = r.nm4z = 0;
-    r.entry = 0;
-    r.boff = 0;
-    r.color = 0;
-    r.ndraw = r.resnaps = 0;
-    r.off = 0;
-    r.rowi = 0;
-    r.d0 = r.d1 = r.d2 = 0.5;
+    ray_clear(r);
     int state = LANE_IDLE;
     int32_t cnt[C_NLOCAL];   // events of the current ray
 #pragma unroll
@@ -2623,18 +2717,10 @@ __global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) march_kernel(Ma
     SeenList<RECORD> sl;
     sl.n = 0;
     uint64_t wmin_key = 0;
-    LkState lk;
-    lk.okey = ~0u;
-    lk.oword = 0;
-    lk.brick_slot = LK == 2 ? reinterpret_cast<uint64_t*>(s_dyn + P.brick_lds_off) + 9 * threadIdx.x : nullptr;
-    DgLane dg;
+    LkState lk = lk_unused();
+    if (LK == 2) lk.brick_slot = reinterpret_cast<uint64_t*>(s_dyn + P.brick_lds_off) + 9 * threadIdx.x;
+    DG_LANE(dg);
 #ifdef VRT_DIAG
-    __shared__ unsigned long long s_dg[VRT_BLOCK / VRT_WAVE][DG_N];
-    dg.acc = (__attribute__((address_space(3))) unsigned long long*)&s_dg[threadIdx.x >> 6][0];
-    if ((threadIdx.x & 63) == 0)
-        for (int j = 0; j < DG_N; j++) dg.acc[j] = 0;
-    dg.brick = ~0u;
-    dg.bv = 0;
     const unsigned long long dg_t_start = __builtin_amdgcn_s_memrealtime();
     unsigned long long dg_t_empty = 0;
     const unsigned long long dg_start = DG_TIME();
@@ -2762,7 +2848,8 @@ __global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) march_kernel(Ma
 // in that view's box under the key the ray has in a frame of that view alone (resnap_commit_views): every view's list is
 // the single frame's.  A workgroup holds rays of several views, so there is no settled bitmap (its bound assumes one box
 // and one increasing ray order): every visit is the load-then-atomicMin of a box without one.  The bodies are the shared
-// ones; LIST / SEED are the two re-trace tiers (the list holds batch offsets).
+// ones, and so are the hand-out (HandOut), the lane set-up (ray_clear, lk_unused, seen_unused, DG_LANE) and the staging of the view
+// records (stage_views); LIST / SEED are the two re-trace tiers (the list holds batch offsets).
 template <int SPEC, int RESMODE, bool LIST, int SEED = 0>
 __global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) march_views_kernel(MarchParams P) {
     static_assert(SPEC >= 4 && SPEC <= 16, "speculation depth");
@@ -2771,80 +2858,32 @@ __global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) march_views_ker
     if (LIST && *P.list_count == 0) return;  // the usual case: no ray ran out of draws
     MarchCtx C;
     march_prologue<false>(P, S, s_dyn, C);
-    {
-        double* s_views = reinterpret_cast<double*>(s_dyn + P.views.view_lds_off);
-        const double* first = P.views.view_tab + (int64_t)P.views.view_first * VRT_VIEW_WORDS;
-        for (int i = threadIdx.x; i < P.views.view_lds * VRT_VIEW_WORDS; i += VRT_BLOCK) s_views[i] = first[i];
-        C.vw = (const lds_char*)s_views;
-    }
+    stage_views(P, s_dyn, C);
     __syncthreads();
 
-    const int64_t count = LIST ? (int64_t)(*P.list_count < P.list_cap ? *P.list_count : P.list_cap) : P.n;
-    const int64_t chunk = P.chunk;
-    int64_t next = 0, range_end = 0;
-    bool more = true;  // the launch-wide counter may still have rays
-    if (chunk == 0) {  // static contiguous range per wave
-        const int64_t n_waves = (int64_t)gridDim.x * (VRT_BLOCK / VRT_WAVE);
-        const int64_t wave = (int64_t)blockIdx.x * (VRT_BLOCK / VRT_WAVE) + (threadIdx.x >> 6);
-        int64_t per = (count + n_waves - 1) / n_waves;
-        per = (per + 7) & ~(int64_t)7;
-        next = wave * per;
-        range_end = next + per < count ? next + per : count;
-        more = false;
-    }
+    HandOut H;
+    H.init(LIST ? (int64_t)(*P.list_count < P.list_cap ? *P.list_count : P.list_cap) : P.n, P.chunk);
 
     Ray r;
-    r.px = r.py = r.pz = r.vx = r.vy = r.vz = 0;
-    r.step = r.life = r.bounces = r.energy = 0;
-    r.nm4x = r.nm4y = r.nm4z = 0;
-    r.entry = 0;
-    r.boff = 0;
-    r.color = 0;
-    r.ndraw = r.resnaps = 0;
-    r.off = 0;
-    r.rowi = 0;
-    r.d0 = r.d1 = r.d2 = 0.5;
-    r.view = 0;
+    ray_clear(r);
     int state = LANE_IDLE;
     int32_t cnt[C_NLOCAL];   // events of the current ray
 #pragma unroll
     for (int j = 0; j < C_NLOCAL; j++) cnt[j] = 0;
-    SeenList<false> sl;
-    sl.n = 0;
-    LkState lk;
-    lk.okey = ~0u;
-    lk.oword = 0;
-    lk.brick_slot = nullptr;
-    DgLane dg;
-#ifdef VRT_DIAG
-    __shared__ unsigned long long s_dg[VRT_BLOCK / VRT_WAVE][DG_N];  // (the bodies count into it; a batched launch reports nothing)
-    dg.acc = (__attribute__((address_space(3))) unsigned long long*)&s_dg[threadIdx.x >> 6][0];
-    if ((threadIdx.x & 63) == 0)
-        for (int j = 0; j < DG_N; j++) dg.acc[j] = 0;
-    dg.brick = ~0u;
-    dg.bv = 0;
-#endif
+    SeenList<false> sl = seen_unused();
+    LkState lk = lk_unused();
+    DG_LANE(dg);
 
     for (;;) {
         // ------------------------------------------------------------------ refill idle lanes
         unsigned long long idle_mask = __ballot(state == LANE_IDLE);
-        while (idle_mask != 0ull && (next < range_end || more)) {
-            if (next >= range_end) {  // take the next chunk (one atomic per wave per chunk)
-                unsigned long long base = 0;
-                if ((threadIdx.x & 63) == 0) base = atomicAdd(P.queue_head, (unsigned long long)chunk);
-                base = wave_first_u64(base);
-                if ((int64_t)base >= count) {
-                    more = false;
-                    break;
-                }
-                next = (int64_t)base;
-                range_end = next + chunk < count ? next + chunk : count;
+        while (idle_mask != 0ull && H.left()) {
+            if (H.used_up()) {
+                H.take_chunk(P.queue_head);
+                if (!H.more) break;
             }
-            const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(idle_mask >> 32),
-                                                            __builtin_amdgcn_mbcnt_lo((unsigned)idle_mask, 0u));
-            const int64_t k = next + rank;
-            next += __popcll(idle_mask);
-            if (state == LANE_IDLE && k < range_end) {
+            const int64_t k = H.hand(idle_mask);
+            if (state == LANE_IDLE && k < H.range_end) {
                 if (take_ray_views<LIST, SEED>(P, C, k, r)) {
 #pragma unroll
                     for (int j = 0; j < C_NLOCAL; j++) cnt[j] = 0;
@@ -2892,6 +2931,7 @@ __global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) march_views_ker
 // no event counters, no seen list, no traversed keys (march_step<.., VIEWS = 3>: a re-snap only moves the chunk cursor), no
 // materials and no pow memo in LDS -- the static LDS is the offset tables and a few scalars; the dynamic LDS the chunk table
 // (if it fits) and, for a batch, the view records.
+// The hand-out, the lane set-up and the view staging are the shared pieces (HandOut, ray_clear .. stage_views above).
 // Record k of the launch goes to P.hits[k] and is ray slot P.ray0 + k * P.slot_stride (VIEWS: of the view k falls into).
 // PERPIX: the ray table holds one record per pixel; VIEWS: the launch's rays belong to several cameras.
 struct FirstHitShared {
@@ -2936,12 +2976,7 @@ __global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) first_hit_kerne
             S.cold[COLD_INV_CS] = 1.0 / (double)P.cs;
         }
         C.vw = nullptr;
-        if (VIEWS) {
-            double* s_views = reinterpret_cast<double*>(s_dyn + P.views.view_lds_off);
-            const double* first = P.views.view_tab + (int64_t)P.views.view_first * VRT_VIEW_WORDS;
-            for (int i = threadIdx.x; i < P.views.view_lds * VRT_VIEW_WORDS; i += VRT_BLOCK) s_views[i] = first[i];
-            C.vw = (const lds_char*)s_views;
-        }
+        if (VIEWS) stage_views(P, s_dyn, C);
         C.tab = (const lds_char*)S.tab;
         C.tl[0] = 0;
         C.tl[1] = 1024;
@@ -2970,36 +3005,14 @@ __global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) first_hit_kerne
     }
     __syncthreads();
 
-    // the hand-out loop of march_kernel: `chunk` consecutive records per wave from a launch-wide counter
-    const int64_t count = P.n;
-    const int64_t chunk = P.chunk;
+    HandOut H;  // (of records)
+    H.init(P.n, P.chunk);
     const uint32_t stride = (uint32_t)P.slot_stride;
     // VIEWS: records per view (the view's slots, or its pixels when only first samples are marched)
     const uint32_t view_recs = VIEWS ? P.views.view_slots / stride : 1u;
-    int64_t next = 0, range_end = 0;
-    bool more = true;
-    if (chunk == 0) {  // static contiguous range per wave
-        const int64_t n_waves = (int64_t)gridDim.x * (VRT_BLOCK / VRT_WAVE);
-        const int64_t wave = (int64_t)blockIdx.x * (VRT_BLOCK / VRT_WAVE) + (threadIdx.x >> 6);
-        int64_t per = (count + n_waves - 1) / n_waves;
-        per = (per + 7) & ~(int64_t)7;
-        next = wave * per;
-        range_end = next + per < count ? next + per : count;
-        more = false;
-    }
 
     Ray r;
-    r.px = r.py = r.pz = r.vx = r.vy = r.vz = 0;
-    r.step = r.life = r.bounces = r.energy = 0;
-    r.nm4x = r.nm4y = r.nm4z = 0;
-    r.entry = 0;
-    r.boff = 0;
-    r.color = 0;
-    r.ndraw = r.resnaps = 0;
-    r.off = 0;
-    r.rowi = 0;
-    r.d0 = r.d1 = r.d2 = 0.5;
-    r.view = 0;
+    ray_clear(r);
     uint32_t rec = 0;        // the record the lane's ray is written to
     int state = LANE_IDLE;
     uint32_t n_rays = 0, n_found = 0;  // wave-uniform: rays traced / rays that found a voxel
@@ -3007,42 +3020,20 @@ __global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) first_hit_kerne
     int32_t cnt[C_NLOCAL];
 #pragma unroll
     for (int j = 0; j < C_NLOCAL; j++) cnt[j] = 0;
-    SeenList<false> sl;
-    sl.n = 0;
-    LkState lk;
-    lk.okey = ~0u;
-    lk.oword = 0;
-    lk.brick_slot = nullptr;
-    DgLane dg;
-#ifdef VRT_DIAG
-    __shared__ unsigned long long s_dg[VRT_BLOCK / VRT_WAVE][DG_N];  // (the bodies count into it; this pass reports nothing)
-    dg.acc = (__attribute__((address_space(3))) unsigned long long*)&s_dg[threadIdx.x >> 6][0];
-    if ((threadIdx.x & 63) == 0)
-        for (int j = 0; j < DG_N; j++) dg.acc[j] = 0;
-    dg.brick = ~0u;
-    dg.bv = 0;
-#endif
+    SeenList<false> sl = seen_unused();
+    LkState lk = lk_unused();
+    DG_LANE(dg);
 
     for (;;) {
         // ------------------------------------------------------------------ refill idle lanes
         unsigned long long idle_mask = __ballot(state == LANE_IDLE);
-        while (idle_mask != 0ull && (next < range_end || more)) {
-            if (next >= range_end) {  // take the next chunk (one atomic per wave per chunk)
-                unsigned long long base = 0;
-                if ((threadIdx.x & 63) == 0) base = atomicAdd(P.queue_head, (unsigned long long)chunk);
-                base = wave_first_u64(base);
-                if ((int64_t)base >= count) {
-                    more = false;
-                    break;
-                }
-                next = (int64_t)base;
-                range_end = next + chunk < count ? next + chunk : count;
+        while (idle_mask != 0ull && H.left()) {
+            if (H.used_up()) {
+                H.take_chunk(P.queue_head);
+                if (!H.more) break;
             }
-            const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(idle_mask >> 32),
-                                                            __builtin_amdgcn_mbcnt_lo((unsigned)idle_mask, 0u));
-            const int64_t k = next + rank;
-            next += __popcll(idle_mask);
-            if (state == LANE_IDLE && k < range_end) {
+            const int64_t k = H.hand(idle_mask);
+            if (state == LANE_IDLE && k < H.range_end) {
                 rec = (uint32_t)k;
                 // the record's ray slot, as an offset in the launch
                 uint32_t slot = rec;
@@ -3232,38 +3223,20 @@ __global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) march_pool_kern
     }
 
     Ray r;
-    r.px = r.py = r.pz = r.vx = r.vy = r.vz = 0;
-    r.step = r.life = r.bounces = r.energy = 0;
-    r.nm4x = r.nm4y = r.nm4z = 0;
-    r.entry = 0;
-    r.boff = 0;
-    r.color = 0;
-    r.ndraw = r.resnaps = 0;
-    r.off = 0;
-    r.rowi = 0;
-    r.d0 = r.d1 = r.d2 = 0.5;
+    ray_clear(r);
     int state = LANE_IDLE;
-    SeenList<false> sl;
-    sl.n = 0;
-    LkState lk;
-    lk.okey = ~0u;
-    lk.oword = 0;
-    lk.brick_slot = nullptr;
+    SeenList<false> sl = seen_unused();
+    LkState lk = lk_unused();
     uint64_t wmin_key = 0;
-    DgLane dg;
+    DG_LANE(dg);
 #ifdef VRT_DIAG
-    __shared__ unsigned long long s_dg[VRT_BLOCK / VRT_WAVE][DG_N];
-    dg.acc = (__attribute__((address_space(3))) unsigned long long*)&s_dg[threadIdx.x >> 6][0];
-    if ((threadIdx.x & 63) == 0)
-        for (int j = 0; j < DG_N; j++) dg.acc[j] = 0;
-    dg.brick = ~0u;
-    dg.bv = 0;
     const unsigned long long dg_t_start = __builtin_amdgcn_s_memrealtime();
     unsigned long long dg_t_empty = 0;
     const unsigned long long dg_start = DG_TIME();
 #endif
 
-    // refill: idle lanes take the next rays of the wave's range (wave-uniform; `lane` etc. from the kernel)
+    // refill: idle lanes take the next rays of the wave's range (wave-uniform; `lane` etc. from the kernel).  HandOut's
+    // loop written out beside the tiled-ticket arm: see march_kernel
     auto refill = [&]() {
         unsigned long long idle_mask = __ballot(state == LANE_IDLE);
 #ifdef VRT_DIAG
@@ -4584,6 +4557,83 @@ __global__ void __launch_bounds__(64) views_setup_kernel(const vrt_camera* cams,
     for (int i = 0; i < 8; i++) out[i] = c[i];
     *reinterpret_cast<int4*>(out + 8) = make_int4(org.o[t][0], org.o[t][1], org.o[t][2], 0);
 }
+// the view table of a batch; traversed: the views' boxes (their origins join the records), or null -- the origins stay 0
+static void setup_views(const vrt_camera* d_cams, const vrt_traversed* traversed, int n_views, int chunk_size, double* view_tab,
+                        hipStream_t stream) {
+    ViewOrigins org;
+    for (int v0 = 0; v0 < n_views; v0 += 64) {
+        const int n = n_views - v0 < 64 ? n_views - v0 : 64;
+        for (int t = 0; t < 64; t++)
+            for (int a = 0; a < 4; a++)
+                org.o[t][a] = (traversed && t < n && a < 3) ? (int32_t)(traversed[v0 + t].origin[a] / chunk_size) : 0;
+        hipLaunchKernelGGL(views_setup_kernel, dim3(1), dim3(64), 0, stream, d_cams, org, v0, n, view_tab);
+    }
+}
+// the camera fill_params checks for a batch: the real ones are on the device (their range is the caller's to check: the
+// march itself reads voxels through a bounds-checked buffer and tests every table and box index it forms)
+static vrt_camera identity_camera() {
+    vrt_camera cam;
+    for (int a = 0; a < 3; a++) cam.pos[a] = cam.rot[a] = 0.0;
+    cam.rot[3] = 1.0;
+    cam.lens = 0.0;
+    return cam;
+}
+// blocks of a resolve launch: enough for either mapping -- which one applies is in the plan header, on the device
+static unsigned resolve_grid(const vrt_settings* st, int64_t n_px) {
+    const int64_t tiles = (int64_t)((st->width + 15) / 16) * ((st->height + 15) / 16);
+    return (unsigned)(grid_for(n_px) > tiles ? grid_for(n_px) : tiles);
+}
+// The three tiers of a frame's or a batch's march: tier 0 marches every ray on `fast_draws` draws of the draw table and
+// lists those that ran out; tier 1 re-traces the listed rays on per-ray rows of D_SLOW draws (device-side count, no host
+// sync; the lane that takes a listed ray seeds its row -- take_ray, SEED -- no launch of its own for that) and lists those
+// that outrun even these; tier 2 re-traces those on D_FULL_DEV draws of a full-state MT19937 (usually empty: the kernel
+// returns at once).  `count`: the launch's counter words -- list counts at +0 / +8, launch-wide ray counters at +2 / +4 / +10.
+struct MarchTiers {
+    const double* table;
+    int32_t fast_draws;
+    double *t_slow, *t_full;
+    uint32_t *list, *list_full, *count;
+    int64_t slow_cap, full_cap;
+};
+static void set_tier(MarchParams& P, const MarchTiers& T, int tier) {
+    P.list_seed = tier;
+    switch (tier) {
+    case 0:  // every ray of the launch, no list
+        P.list = nullptr;
+        P.list_count = nullptr;
+        P.list_cap = 0;
+        P.draws = T.table;
+        P.n_draws = P.draw_stride = T.fast_draws;
+        P.retrace_list = T.list;
+        P.retrace_count = T.count;
+        P.retrace_cap = (uint32_t)T.slow_cap;
+        P.queue_head = (unsigned long long*)(T.count + 2);
+        break;
+    case 1:
+        P.list = T.list;
+        P.list_count = T.count;
+        P.list_cap = (uint32_t)T.slow_cap;
+        P.draws = T.t_slow;
+        P.n_draws = D_SLOW;
+        P.draw_stride = VRT_SLOW_STRIDE;
+        P.retrace_list = T.list_full;
+        P.retrace_count = T.count + 8;
+        P.retrace_cap = (uint32_t)T.full_cap;
+        P.queue_head = (unsigned long long*)(T.count + 4);
+        break;
+    default:  // the last tier lists nothing
+        P.list = T.list_full;
+        P.list_count = T.count + 8;
+        P.list_cap = (uint32_t)T.full_cap;
+        P.draws = T.t_full;
+        P.n_draws = P.draw_stride = D_FULL_DEV;
+        P.retrace_list = nullptr;
+        P.retrace_count = nullptr;
+        P.retrace_cap = 0;
+        P.queue_head = (unsigned long long*)(T.count + 10);
+        break;
+    }
+}
 struct ViewsLayout {
     int64_t slots;       // ray slots per view
     int64_t per_launch;  // views per march launch
@@ -4795,6 +4845,8 @@ int vrt_render_tile(const vrt_scene* scene, const vrt_settings* st, const vrt_ca
     P.per_pixel = per_pixel;
     P.lens = cam->lens;
     P.tab = tab;
+    const MarchTiers tiers = {table, fast_draws, t_slow, (double*)(ws + w.off_full), list, (uint32_t*)(ws + w.off_list_full), count,
+                              w.slow_cap, w.full_cap};
     for (int64_t ray0 = 0; ray0 < rays; ray0 += w.batch) {
         const int64_t n = (rays - ray0) < w.batch ? (rays - ray0) : w.batch;
         if (ray0 != 0) clear_words(count, 256 + 8 * 128, stream);  // retrace counts + the launch-wide ray counters (first batch: frame_begin_kernel)
@@ -4802,15 +4854,7 @@ int vrt_render_tile(const vrt_scene* scene, const vrt_settings* st, const vrt_ca
         P.n = n;
         P.chunk = march_chunk(n);
         march_policy(big_scene, n, P.t_hit, P.t_end, P.max_iters);
-        P.list = nullptr;
-        P.list_count = nullptr;
-        P.draws = table;
-        P.n_draws = fast_draws;
-        P.draw_stride = fast_draws;
-        P.retrace_list = list;
-        P.retrace_count = count;
-        P.retrace_cap = (uint32_t)w.slow_cap;
-        P.queue_head = (unsigned long long*)(count + 2);
+        set_tier(P, tiers, 0);
         // (the pool variant may give up the settled bitmap for its LDS: decided on a copy, the re-traces keep theirs)
         MarchParams F = P;
         F.wt_on = !d_rays && march_wt_ok(P, resmode, deep);
@@ -4842,49 +4886,20 @@ int vrt_render_tile(const vrt_scene* scene, const vrt_settings* st, const vrt_ca
                         : launch_march<false, false>(F, march_grid(n), resmode, deep, pool, stream);
             if (rc != VRT_OK) return rc;
         }
-        // rays that ran out of draws: per-ray 113-draw rows, device-side count (no host sync); the lane that takes a listed ray
-        // seeds its row (take_ray, SEED: no launch of its own for that)
+        // the re-trace tiers (set_tier): rays that ran out of draws, then those that outrun even D_SLOW draws
         ProfScope ps(stream, VRT_PROF_RETRACE);
-        const int rgrid = 256;
-        uint32_t* list_full = (uint32_t*)(ws + w.off_list_full);
-        double* t_full = (double*)(ws + w.off_full);
-        P.list = list;
-        P.list_count = count;
-        P.draws = t_slow;
-        P.n_draws = D_SLOW;
-        P.draw_stride = VRT_SLOW_STRIDE;
-        P.list_cap = (uint32_t)w.slow_cap;
-        P.retrace_list = list_full;  // rays that outrun even 113 draws: third tier below
-        P.retrace_count = count + 8;
-        P.retrace_cap = (uint32_t)w.full_cap;
-        P.queue_head = (unsigned long long*)(count + 4);
+        set_tier(P, tiers, 1);
         P.prefix_draws = pool ? fast_draws : 0;  // (see hit_body)
-        P.list_seed = 1;
-        if (d_rays) launch_march<true, true>(P, rgrid, resmode, deep, false, stream);
-        else launch_march<false, true>(P, rgrid, resmode, deep, false, stream);
+        if (d_rays) launch_march<true, true>(P, 256, resmode, deep, false, stream);
+        else launch_march<false, true>(P, 256, resmode, deep, false, stream);
         P.prefix_draws = 0;
-        // third tier: full-state MT19937, D_FULL_DEV draws per ray; usually empty (the kernel returns at once)
-        P.list_seed = 2;
-        P.list = list_full;
-        P.list_count = count + 8;
-        P.draws = t_full;
-        P.n_draws = D_FULL_DEV;
-        P.draw_stride = D_FULL_DEV;
-        P.list_cap = (uint32_t)w.full_cap;
-        P.retrace_list = nullptr;
-        P.retrace_count = nullptr;
-        P.retrace_cap = 0;
-        P.queue_head = (unsigned long long*)(count + 10);
+        set_tier(P, tiers, 2);
         if (d_rays) launch_march<true, true>(P, 64, resmode, deep, false, stream);
         else launch_march<false, true>(P, 64, resmode, deep, false, stream);
-        P.list_seed = 0;
     }
     if (d_rgba_f32 || d_image_u8) {
         ProfScope ps(stream, VRT_PROF_RESOLVE);
-        // (grid: enough for either mapping -- which one applies is in the plan header, on the device)
-        const int64_t tiles = (int64_t)((st->width + 15) / 16) * ((st->height + 15) / 16);
-        const int64_t rgrid = grid_for(n_px) > tiles ? grid_for(n_px) : tiles;
-        hipLaunchKernelGGL(resolve_kernel, dim3((unsigned)rgrid), dim3(VRT_BLOCK), 0, stream, *st, g, (const PlanHeader*)d_plan, rgba,
+        hipLaunchKernelGGL(resolve_kernel, dim3(resolve_grid(st, n_px)), dim3(VRT_BLOCK), 0, stream, *st, g, (const PlanHeader*)d_plan, rgba,
                            d_rgba_f32, d_image_u8);
     }
     HIP_TRY(hipGetLastError());
@@ -4908,13 +4923,7 @@ int vrt_render_views(const vrt_scene* scene, const vrt_settings* st, const vrt_c
     if (d_rays) return VRT_ERR_ARG;                                      // no debug records of a batch
     if (!st || st->seed_nonce != 0) return VRT_ERR_ARG;                  // static seeds only: a batch exists to reuse the cached tables
     if (!d_draw_table || !d_ray_table) return VRT_ERR_ARG;
-    // the scene and settings checks of a frame; the cameras are on the device (their range is the caller's to check: the
-    // march itself reads voxels through a bounds-checked buffer and tests every table and box index it forms)
-    vrt_camera cam0;
-    for (int a = 0; a < 3; a++) cam0.pos[a] = 0.0;
-    cam0.rot[0] = cam0.rot[1] = cam0.rot[2] = 0.0;
-    cam0.rot[3] = 1.0;
-    cam0.lens = 0.0;
+    const vrt_camera cam0 = identity_camera();  // (the scene and settings checks of a frame)
     MarchParams P;
     int rc = fill_params(P, scene, st, &cam0, nullptr, d_stats);
     if (rc != VRT_OK) return rc;
@@ -4925,7 +4934,6 @@ int vrt_render_views(const vrt_scene* scene, const vrt_settings* st, const vrt_c
     if ((int64_t)n_views * slots >= 4294967295ll) return VRT_ERR_ARG;
     if (n_distinct < 0 || n_distinct > slots || !fast_draws_ok(fast_draws)) return VRT_ERR_ARG;
     // the traversed boxes: equal dimensions, an origin each, the keys view after view in one allocation
-    ViewOrigins org;
     uint64_t* keys = nullptr;
     int64_t tcells = 0;
     if (traversed && traversed[0].d_keys) {
@@ -4971,13 +4979,7 @@ int vrt_render_views(const vrt_scene* scene, const vrt_settings* st, const vrt_c
                            (unsigned long long*)keys, n_keys);
     }
     if (n_px == 0) return VRT_OK;
-    for (int v0 = 0; v0 < n_views; v0 += 64) {
-        const int n = n_views - v0 < 64 ? n_views - v0 : 64;
-        for (int t = 0; t < 64; t++)
-            for (int a = 0; a < 4; a++)
-                org.o[t][a] = (keys && t < n && a < 3) ? (int32_t)(traversed[v0 + t].origin[a] / st->chunk_size) : 0;
-        hipLaunchKernelGGL(views_setup_kernel, dim3(1), dim3(64), 0, stream, d_cams, org, v0, n, view_tab);
-    }
+    setup_views(d_cams, keys ? traversed : nullptr, n_views, st->chunk_size, view_tab, stream);
     TileGeom g;
     g.pixels = d_pixels_xy;
     g.n_px = n_px;
@@ -4996,6 +4998,9 @@ int vrt_render_views(const vrt_scene* scene, const vrt_settings* st, const vrt_c
     P.views.view_tab = view_tab;
     P.views.view_slots = (uint32_t)slots;
     P.views.view_recip = slots > 1 ? (uint32_t)(((uint64_t)1 << 32) / (uint64_t)slots) : 0xffffffffu;
+    const MarchTiers tiers = {d_draw_table, fast_draws, t_slow, (double*)(ws + w.off_full), list, (uint32_t*)(ws + w.off_list_full),
+                              count, w.slow_cap, w.full_cap};
+    P.prefix_draws = 0;  // (lanes count per ray, as in march_kernel: nothing to take off again)
     for (int64_t v0 = 0; v0 < n_views; v0 += w.per_launch) {
         const int64_t nv = n_views - v0 < w.per_launch ? n_views - v0 : w.per_launch;
         const int64_t n = nv * slots;
@@ -5005,53 +5010,21 @@ int vrt_render_views(const vrt_scene* scene, const vrt_settings* st, const vrt_c
         P.n = n;
         P.chunk = march_chunk(n);
         march_policy(big_scene, n, P.t_hit, P.t_end, P.max_iters);
-        P.list = nullptr;
-        P.list_count = nullptr;
-        P.list_seed = 0;
-        P.prefix_draws = 0;  // (lanes count per ray, as in march_kernel: nothing to take off again)
-        P.draws = d_draw_table;
-        P.n_draws = fast_draws;
-        P.draw_stride = fast_draws;
-        P.retrace_list = list;
-        P.retrace_count = count;
-        P.retrace_cap = (uint32_t)w.slow_cap;
-        P.queue_head = (unsigned long long*)(count + 2);
+        set_tier(P, tiers, 0);
         {
             ProfScope ps(stream, VRT_PROF_MARCH);
             launch_march_views<false>(P, march_grid(n), resmode, nv, stream);
         }
         // the two re-trace tiers of vrt_render_tile; their lists hold offsets in this launch, the view follows from them
         ProfScope ps(stream, VRT_PROF_RETRACE);
-        P.list = list;
-        P.list_count = count;
-        P.draws = t_slow;
-        P.n_draws = D_SLOW;
-        P.draw_stride = VRT_SLOW_STRIDE;
-        P.list_cap = (uint32_t)w.slow_cap;
-        P.retrace_list = (uint32_t*)(ws + w.off_list_full);
-        P.retrace_count = count + 8;
-        P.retrace_cap = (uint32_t)w.full_cap;
-        P.queue_head = (unsigned long long*)(count + 4);
-        P.list_seed = 1;
+        set_tier(P, tiers, 1);
         launch_march_views<true>(P, 256, resmode, nv, stream);
-        P.list_seed = 2;
-        P.list = (uint32_t*)(ws + w.off_list_full);
-        P.list_count = count + 8;
-        P.draws = (double*)(ws + w.off_full);
-        P.n_draws = D_FULL_DEV;
-        P.draw_stride = D_FULL_DEV;
-        P.list_cap = (uint32_t)w.full_cap;
-        P.retrace_list = nullptr;
-        P.retrace_count = nullptr;
-        P.retrace_cap = 0;
-        P.queue_head = (unsigned long long*)(count + 10);
+        set_tier(P, tiers, 2);
         launch_march_views<true>(P, 64, resmode, nv, stream);
     }
     if (d_rgba_f32 || d_image_u8) {
         ProfScope ps(stream, VRT_PROF_RESOLVE);
-        const int64_t tiles = (int64_t)((st->width + 15) / 16) * ((st->height + 15) / 16);
-        const int64_t rgrid = grid_for(n_px) > tiles ? grid_for(n_px) : tiles;
-        hipLaunchKernelGGL(resolve_views_kernel, dim3((unsigned)rgrid, (unsigned)(n_views < 65535 ? n_views : 65535)), dim3(VRT_BLOCK), 0, stream,
+        hipLaunchKernelGGL(resolve_views_kernel, dim3(resolve_grid(st, n_px), (unsigned)(n_views < 65535 ? n_views : 65535)), dim3(VRT_BLOCK), 0, stream,
                            *st, g, (const PlanHeader*)d_plan, (int)n_views, rgba, d_rgba_f32, d_image_u8);
     }
     HIP_TRY(hipGetLastError());
@@ -5157,13 +5130,7 @@ int vrt_first_hit_views(const vrt_scene* scene, const vrt_settings* st, const vr
                         void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!d_cams || n_views < 1) return VRT_ERR_ARG;
-    // the scene and settings checks of a frame; the cameras are on the device (their range is the caller's to check: see
-    // vrt_render_views)
-    vrt_camera cam0;
-    for (int a = 0; a < 3; a++) cam0.pos[a] = 0.0;
-    cam0.rot[0] = cam0.rot[1] = cam0.rot[2] = 0.0;
-    cam0.rot[3] = 1.0;
-    cam0.lens = 0.0;
+    const vrt_camera cam0 = identity_camera();  // (the scene and settings checks of a frame)
     MarchParams P;
     int rc = fill_params(P, scene, st, &cam0, nullptr, d_stats);
     if (rc != VRT_OK) return rc;
@@ -5174,11 +5141,7 @@ int vrt_first_hit_views(const vrt_scene* scene, const vrt_settings* st, const vr
     double* view_tab = (double*)d_workspace;
     frame_begin(d_stats, nullptr, 0, nullptr, 0, nullptr, stream);
     if (n_px == 0) return VRT_OK;
-    ViewOrigins org;  // (no traversed boxes: the origins of the records stay 0)
-    for (int t = 0; t < 64; t++)
-        for (int a = 0; a < 4; a++) org.o[t][a] = 0;
-    for (int v0 = 0; v0 < n_views; v0 += 64)
-        hipLaunchKernelGGL(views_setup_kernel, dim3(1), dim3(64), 0, stream, d_cams, org, v0, n_views - v0 < 64 ? n_views - v0 : 64, view_tab);
+    setup_views(d_cams, nullptr, n_views, st->chunk_size, view_tab, stream);  // (no traversed boxes)
     const int64_t slots = n_px * P.g.smax;
     const int64_t stride = first_sample_only ? P.g.smax : 1;
     const int64_t view_recs = first_sample_only ? n_px : slots;

@@ -172,3 +172,34 @@ def check_tile_plan(dp, st):
     assert (idx[used] < len(distinct)).all()
     assert np.array_equal(seed_list[idx[used]].astype(np.int64), seeds[used])
     return hdr
+
+
+# the hand-out's operating points besides the shipped one: the static range per wave, with the usual and an odd small grid;
+# small chunks over an odd grid; one workgroup that takes every chunk
+HANDOUT_KNOBS = [{}, {"VRT_CHUNK": "0"}, {"VRT_CHUNK": "0", "VRT_MARCH_GRID": "3"}, {"VRT_CHUNK": "64", "VRT_MARCH_GRID": "7"},
+                 {"VRT_MARCH_GRID": "1"}]
+
+
+def run_children(call, knob_sets, tag):
+    """`call` (python source) in one child process per set of scheduling knobs -- they are read once per process --, all at
+    once; returns each child's line that begins with `tag`, split into words."""
+    import os
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))   # (tests/: the children import the test modules)
+    base = {k: v for k, v in os.environ.items() if k not in ("VRT_CHUNK", "VRT_MARCH_GRID")}
+    procs = [subprocess.Popen([sys.executable, "-c", call], cwd=here, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
+                              env=dict(base, PYTHONPATH=os.pathsep.join([here, os.path.dirname(here)]), **knobs))
+             for knobs in knob_sets]
+    lines = []
+    try:
+        for knobs, proc in zip(knob_sets, procs):
+            out = proc.communicate(timeout=120)[0]
+            assert proc.returncode == 0, (knobs, out)
+            lines.append([l for l in out.splitlines() if l.startswith(tag)][0].split())
+    finally:   # (a failure leaves no child behind on the GPU)
+        for proc in procs:
+            if proc.poll() is None:
+                proc.kill()
+            proc.wait()
+    return lines

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
-from gpu_util import camera_for, settings_store
+from gpu_util import HANDOUT_KNOBS, camera_for, run_children, settings_store
 from python_raytracer_amd import _native as nat
 
 gpu = pytest.mark.gpu
@@ -320,6 +320,44 @@ def test_more_views_than_lds_holds():
         assert_records_equal(got[v].numpy(), cam.first_hit(0, all_samples=True).numpy())
     mats = np.concatenate([g.numpy()["material"] for g in got])
     assert 0.1 < (mats > 0).mean() < 0.9 and len(set(mats[mats > 0].tolist())) >= 3
+
+
+# ---- the hand-out of first_hit_kernel ----------------------------------------------------------------------------------
+def _handout_child():
+    """The 64^3 synthetic scene at 31 x 23: every sample, first samples only, and a batch of 3 poses, with one ray record per
+    slot and one per pixel; prints one digest, the rays traced and the voxels found per call."""
+    import hashlib
+    sc = ol.synth64_scene()
+    words = []
+    for per_pixel in (False, True):
+        st = ol.make_settings(width=31, height=23, samples=SAMPLES, **(dict(dof=0.0, lod_random=0.0, lod_samples=0.0) if per_pixel else {}))
+        cam = camera_for(id_scene(sc), settings_store(st), sc.cam_pos, sc.cam_rot, sc.cam_lens)
+        rng = np.random.default_rng(31)
+        poses = [(tuple(sc.cam_pos), tuple(sc.cam_rot))]
+        for _ in range(2):
+            q = np.array(sc.cam_rot) + rng.normal(size=4) * 0.25
+            poses.append((tuple(np.array(sc.cam_pos) + rng.uniform(-6, 6, 3)), tuple(q / np.linalg.norm(q))))
+        every = cam.first_hit(0, all_samples=True)
+        assert every.numpy().size % 64 != 0 and (every.numpy()["material"] == -1).any(), "no unused sample slot"
+        first = cam.first_hit(0, all_samples=False)
+        assert first.numpy().size == 31 * 23
+        views = cam.first_hit_views(poses, all_samples=True)
+        for recs, stats in ((every.numpy(), every.stats), (first.numpy(), first.stats),
+                            (np.concatenate([v.numpy() for v in views]), views[0].stats)):
+            words += [hashlib.sha256(np.ascontiguousarray(recs).tobytes()).hexdigest(), str(int(stats[8])), str(int(stats[4]))]
+    print("HANDOUT", " ".join(words))
+
+
+@gpu
+def test_first_hit_does_not_depend_on_the_hand_out():
+    """first_hit_kernel, one camera and several, both ray-table layouts, under the scheduling knobs the frame kernels are tested
+    with: the records, the rays traced and the voxels found are the same (the default setting is pinned to the oracle above)."""
+    lines = run_children("import test_gpu_first_hit as t; t._handout_child()", HANDOUT_KNOBS, "HANDOUT")
+    assert len(lines[0]) == 1 + 2 * 3 * 3
+    for knobs, words in zip(HANDOUT_KNOBS, lines):
+        print(knobs, [w[:12] for w in words[1:]])
+    for knobs, words in zip(HANDOUT_KNOBS[1:], lines[1:]):
+        assert words == lines[0], (knobs, words, lines[0])
 
 
 # ---- 8. graph capture ------------------------------------------------------------------------------------------------

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
-from gpu_util import camera_for, settings_store, sparse_scene
+from gpu_util import HANDOUT_KNOBS, camera_for, run_children, settings_store, sparse_scene
 from python_raytracer_amd import _native as nat
 
 gpu = pytest.mark.gpu
@@ -194,7 +194,7 @@ def _split_child():
     """Run in a child process with VRT_BATCH_LOG2=12 (read once per process): 20 views of 495 slots are then marched as three
     launches of 8 + 8 + 4 views, more views than the first launch holds; prints one digest of the batch and one of the
     single frames."""
-    st = settings(max_bounces=16.0, max_light=100.0, lod_bounces=0.0)   # (rays that re-trace, in every launch)
+    st = settings(max_bounces=16.0, max_light=100.0, lod_bounces=0.0)   # (the re-trace tests' settings; this scene's rays stay within 32 draws: _handout_child)
     rng = np.random.default_rng(20)
     poses = []
     for _ in range(20):
@@ -231,16 +231,50 @@ def test_batch_split_into_launches_at_view_boundaries():
     assert words[1] == words[2] and int(words[3]) > 20 * 400
 
 
-# weakly absorbing rough materials: many rough hits per ray, three draws each
-MATS_BOUNCY = np.array([[200, 180, 160, 1.0, 0.05, 1.0, 0.0], [90, 120, 250, 0.5, 0.05, 0.5, 0.0], [60, 200, 90, 0.1, 0.5, 0.75, 0.0],
-                        [230, 230, 230, 0.0, 2.0, 1.0, 0.0]])
+def _handout_child():
+    """_split_child's scene and settings (rays that re-trace: the LIST instances hand out too), 5 views of 495 slots -- 2 475 is
+    no multiple of 64 or 128; prints one digest per batch and the statistics."""
+    st = settings(max_bounces=16.0, max_light=100.0, lod_bounces=0.0)
+    rng = np.random.default_rng(20)
+    poses = []
+    for _ in range(5):
+        q = rng.normal(size=4)
+        poses.append((tuple(rng.uniform(-20, 20, 3)), tuple(q / np.linalg.norm(q))))
+    cam = camera_for(scene(3), settings_store(st), *poses[0], lens_of(st))
+    cam.fast_draws = 32
+    got = cam.render_views(poses, want_ray_rgba=True)
+    assert len(got) == 5 and got[0].ray_rgba.numel() == 495
+    # (the CPU oracle finds at most 4 rough hits per ray in that scene -- 15 draws -- so none of its rays outruns 32 draws;
+    # the re-trace instances get their rays from the weakly absorbing scene of test_retraces_in_a_batch, 5 views as well)
+    st2 = settings(max_bounces=16.0, max_light=100.0, lod_bounces=0.0, falloff=0.0)
+    poses2 = BOUNCY_POSES + [((-1.2, 0.9, 1.1), IDENTITY), ((0.3, 0.6, 0.45), ROTATED)]
+    cam2 = camera_for(bouncy_scene(), settings_store(st2), *poses2[0], lens_of(st2))
+    cam2.fast_draws = 32
+    got2 = cam2.render_views(poses2, want_ray_rgba=True)
+    assert len(got2) == 5 and got2[0].ray_rgba.numel() == 495
+    print("HANDOUT", digest(got), digest(got2), " ".join(str(int(v)) for v in list(got[0].stats[:12]) + list(got2[0].stats[:12])))
 
 
 @gpu
-def test_retraces_in_a_batch():
-    """Rays that outrun the 32-draw table are re-traced from a list of batch offsets, with 113-draw rows and (the few that
-    outrun those) 1 024-draw rows: both tiers must find their ray's view again.  15 x 11 x 3 is enough: the single frames
-    re-trace at this size (asserted)."""
+def test_batch_does_not_depend_on_the_hand_out():
+    """march_views_kernel and its two re-trace instances under the scheduling knobs the frame kernels are tested with
+    (test_scheduling_knobs_do_not_change_results): images, per-ray colours, traversed lists and statistics are the same."""
+    lines = run_children("import test_gpu_views as t; t._handout_child()", HANDOUT_KNOBS, "HANDOUT")
+    for knobs, words in zip(HANDOUT_KNOBS, lines):
+        print(knobs, words[1][:16], words[2][:16], words[3:])
+    assert len(lines[0]) == 3 + 24
+    assert int(lines[0][3 + 12 + 9]) > 0, "no ray was re-traced"
+    for knobs, words in zip(HANDOUT_KNOBS[1:], lines[1:]):
+        assert words[1:] == lines[0][1:], (knobs, words, lines[0])
+
+
+# weakly absorbing rough materials: many rough hits per ray, three draws each
+MATS_BOUNCY = np.array([[200, 180, 160, 1.0, 0.05, 1.0, 0.0], [90, 120, 250, 0.5, 0.05, 0.5, 0.0], [60, 200, 90, 0.1, 0.5, 0.75, 0.0],
+                        [230, 230, 230, 0.0, 2.0, 1.0, 0.0]])
+BOUNCY_POSES = [((0.3, 0.6, 0.45), IDENTITY), ((1.3, -0.4, 0.45), ROTATED), ((0.3, 0.6, 0.45), IDENTITY)]
+
+
+def bouncy_scene():
     rng = np.random.default_rng(411)
     dims = np.array([4, 4, 4])
     origin = -(dims // 2) * CS
@@ -249,9 +283,17 @@ def test_retraces_in_a_batch():
     res = np.ones(tuple(dims), np.uint8)
     grid = np.where(rng.random(shape) < 0.3, rng.integers(1, 5, shape), 0).astype(np.uint8)
     grid[12:20, 12:20, 12:20] = 0   # a pocket round the cameras
-    sc = ol.Scene(origin, dims, CS, present, res, ol.Scene.camera_grid(grid, origin, dims, CS, present, res), MATS_BOUNCY)
+    return ol.Scene(origin, dims, CS, present, res, ol.Scene.camera_grid(grid, origin, dims, CS, present, res), MATS_BOUNCY)
+
+
+@gpu
+def test_retraces_in_a_batch():
+    """Rays that outrun the 32-draw table are re-traced from a list of batch offsets, with 113-draw rows and (the few that
+    outrun those) 1 024-draw rows: both tiers must find their ray's view again.  15 x 11 x 3 is enough: the single frames
+    re-trace at this size (asserted)."""
+    sc = bouncy_scene()
     st = settings(max_bounces=16.0, max_light=100.0, lod_bounces=0.0, falloff=0.0)
-    poses = [((0.3, 0.6, 0.45), IDENTITY), ((1.3, -0.4, 0.45), ROTATED), ((0.3, 0.6, 0.45), IDENTITY)]
+    poses = BOUNCY_POSES
     cam = camera_for(sc, settings_store(st), *poses[0], lens_of(st))
     ref = []
     for p in poses:
