@@ -189,6 +189,9 @@ def lib():
     L.vrt_profile_end.argtypes = [vp, vp]
     L.vrt_synth_volume.restype = C.c_int
     L.vrt_synth_volume.argtypes = [i32, i32, vp, vp, vp]
+    # diagnostic, not part of include/vrt.h: what the calling thread's last frame-march launch kept in LDS (PLAN_* below)
+    L.vrt_diag_last_plan.restype = C.c_int
+    L.vrt_diag_last_plan.argtypes = [C.POINTER(i64), C.c_int]
     if L.vrt_abi_version() != ABI_VERSION:
         raise ImportError("python_raytracer_amd/_vrt.so has ABI version %d, expected %d"
                           % (L.vrt_abi_version(), ABI_VERSION))
@@ -204,6 +207,26 @@ EXPORTS = ["vrt_abi_version", "vrt_status_string", "vrt_last_hip_error", "vrt_de
            "vrt_pow_memo_create", "vrt_occupancy_build", "vrt_canvas_blit", "vrt_world_tables_bytes", "vrt_world_tables_build",
            "vrt_trace_workspace_bytes", "vrt_trace_rays", "vrt_rng_draws",
            "vrt_synth_volume", "vrt_profile_begin", "vrt_profile_begin_kinds", "vrt_profile_end", "vrt_select_chunks", "vrt_voxelize"]
+
+
+PLAN_FIELDS = ("launches", "pool", "wt_on", "trav_words", "bm_window", "ct_cells", "n_materials", "dyn_bytes", "static_bytes")
+PLAN_PROBE_FIELDS = ("wt_on", "trav_words", "dyn_bytes", "static_bytes", "groups_per_cu")
+
+
+def last_plan():
+    """vrt_diag_last_plan as a dict: PLAN_FIELDS of the calling thread's last frame-march launch, and `probes`: one dict of
+    PLAN_PROBE_FIELDS per configuration the ray pool's planner asked the runtime about, in the order it tried them."""
+    L = lib()
+    n = L.vrt_diag_last_plan((C.c_int64 * 1)(), 0)
+    if n < 0:
+        check(n, "vrt_diag_last_plan")
+    buf = (C.c_int64 * n)()
+    L.vrt_diag_last_plan(buf, n)
+    w = [int(v) for v in buf]
+    plan = dict(zip(PLAN_FIELDS, w))
+    k = len(PLAN_FIELDS) + 1
+    plan["probes"] = [dict(zip(PLAN_PROBE_FIELDS, w[k + 5 * i:k + 5 * i + 5])) for i in range(w[len(PLAN_FIELDS)])]
+    return plan
 
 
 def check(status, what):

@@ -4348,6 +4348,48 @@ static inline size_t march_lds(MarchParams& P, bool bricks, bool pool) {
     if (pool) n += (size_t)(VRT_BLOCK / VRT_WAVE) * VRT_POOL_WAVE_BYTES;
     return n + 16;
 }
+// What the last frame-march launch of this thread chose to keep in LDS (vrt_diag_last_plan; host memory only).  Words:
+// 0 launches recorded so far on this thread | 1 the ray pool ran | 2 wt_on | 3 trav_words | 4 bm_window | 5 ct_cells |
+// 6 n_materials | 7 dynamic LDS bytes of the launch | 8 static LDS bytes of its kernel | 9 configurations pool_plan asked
+// the runtime about, in the order it tried them (the last one is the chosen one if the pool ran), then 5 words each:
+// wt_on, trav_words, dynamic bytes, static bytes, workgroups per CU the runtime answered.
+#define VRT_PLAN_PROBES 4
+#define VRT_PLAN_WORDS (10 + 5 * VRT_PLAN_PROBES)
+struct PlanRecord {
+    int64_t w[VRT_PLAN_WORDS];
+    bool probes_fresh;  // pool_plan ran for the launch that comes next
+};
+static thread_local PlanRecord g_plan = {{0}, false};
+// static LDS of a frame-march kernel: its MarchSharedT, padded to the 16-byte boundary the dynamic part starts at
+static inline int64_t plan_static_bytes(bool w) {
+    return (int64_t)(((w ? sizeof(MarchSharedT<true>) : sizeof(MarchShared)) + 15) & ~(size_t)15);
+}
+static void plan_probe(const MarchParams& P, size_t dyn, bool w, int nb) {
+    if (!g_plan.probes_fresh) {
+        g_plan.probes_fresh = true;
+        g_plan.w[9] = 0;
+    }
+    if (g_plan.w[9] >= VRT_PLAN_PROBES) return;
+    int64_t* q = g_plan.w + 10 + 5 * g_plan.w[9]++;
+    q[0] = P.wt_on;
+    q[1] = P.trav_words;
+    q[2] = (int64_t)dyn;
+    q[3] = plan_static_bytes(w);
+    q[4] = nb;
+}
+static void plan_record(const MarchParams& P, size_t dyn, bool pool) {
+    if (!g_plan.probes_fresh) g_plan.w[9] = 0;
+    g_plan.probes_fresh = false;
+    g_plan.w[0]++;
+    g_plan.w[1] = pool ? 1 : 0;
+    g_plan.w[2] = P.wt_on;
+    g_plan.w[3] = P.trav_words;
+    g_plan.w[4] = P.bm_window;
+    g_plan.w[5] = P.ct_cells;
+    g_plan.w[6] = P.n_materials;
+    g_plan.w[7] = (int64_t)dyn;
+    g_plan.w[8] = plan_static_bytes(P.wt_on != 0);
+}
 // workgroups of march_pool_kernel a CU holds with `dyn` bytes of dynamic LDS (the runtime's own occupancy calculation)
 static int pool_blocks_per_cu(size_t dyn, bool w) {
     static std::mutex mu;
@@ -4372,6 +4414,12 @@ static int pool_blocks_per_cu(size_t dyn, bool w) {
 }
 // Does the frame's march of this launch use the ray pool?  Only if VRT_WAVES_PER_SIMD workgroups still fit a CU with the
 // pools in LDS -- without the settled bitmap if need be (P.trav_words is cleared then).
+static bool pool_fits(MarchParams& P, bool w) {
+    const size_t dyn = march_lds(P, false, true);
+    const int nb = pool_blocks_per_cu(dyn, w);
+    plan_probe(P, dyn, w, nb);
+    return nb >= VRT_WAVES_PER_SIMD;
+}
 static bool pool_plan(MarchParams& P) {
     if (!march_pool() || lookup_mode() != 0) return false;
     // a wave's pool holds up to 64 + VRT_POOL_SLOTS rays when the launch runs out of new ones, and drains alone: small
@@ -4382,9 +4430,10 @@ static bool pool_plan(MarchParams& P) {
     for (int keep_wt = wt; keep_wt >= 0; keep_wt--) {  // (the world-axis tables are given up before the pool is)
         P.wt_on = keep_wt;
         P.trav_words = words;
-        if (pool_blocks_per_cu(march_lds(P, false, true), keep_wt != 0) >= VRT_WAVES_PER_SIMD) return true;
+        if (pool_fits(P, keep_wt != 0)) return true;
+        if (words == 0) continue;  // (nothing more to give up at this step)
         P.trav_words = 0;
-        if (pool_blocks_per_cu(march_lds(P, false, true), keep_wt != 0) >= VRT_WAVES_PER_SIMD) return true;
+        if (pool_fits(P, keep_wt != 0)) return true;
     }
     P.trav_words = words;
     P.wt_on = wt;
@@ -4401,6 +4450,7 @@ static int launch_march(MarchParams P, int grid, int resmode, bool deep, bool po
         // called settled (see trav_cell) -- every visit compares its key with the cell's.
         if (LIST) P.trav_words = 0;
         const size_t lds = march_lds(P, false, false);
+        if (!LIST) plan_record(P, lds, false);
         if (LIST && P.list_seed == 1)
             hipLaunchKernelGGL((march_kernel<VRT_SPEC, 2, RECORD, LIST, 0, 4, false, false, LIST ? 1 : 0>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
         else if (LIST && P.list_seed == 2)
@@ -4412,6 +4462,7 @@ static int launch_march(MarchParams P, int grid, int resmode, bool deep, bool po
     if (pool) {
         pool_policy(P, (int64_t)P.vox_bytes > ((int64_t)512 << 20));
         const size_t lds = march_lds(P, false, true);
+        plan_record(P, lds, true);
 #define VRT_LAUNCH_POOL_W(SPEC_, RES_, W_)                                                                                 \
     do {                                                                                                                   \
         if (P.per_pixel)                                                                                                   \
@@ -4472,6 +4523,7 @@ static int launch_march(MarchParams P, int grid, int resmode, bool deep, bool po
     if (P.bm_window >= 0 && !P.wt_on && lk == 0 && deep && VRT_SPEC_DEEP == 8 && resmode != 2 && P.t_keys && march_defer(P))
         P.trav_words = 0;  // (march_kernel's DEFER instances have no code for one)
     const size_t lds = march_lds(P, lk == 2, false);
+    plan_record(P, lds, false);
     if (P.wt_on) {  // (only with 8 positions, resolutions <= 2 and the byte lookup: march_wt_ok)
 #define VRT_LAUNCH_W(RES_)                                                                                                          \
     do {                                                                                                                            \
@@ -5274,6 +5326,15 @@ int vrt_select_chunks(const uint32_t* d_world_table, const int64_t* origin, cons
     hipLaunchKernelGGL(select_chunks_kernel, dim3(grid_for(n)), dim3(VRT_BLOCK), 0, stream, S, d_world_table, d_camera_table);
     HIP_TRY(hipGetLastError());
     return VRT_OK;
+}
+
+// Diagnostic, outside include/vrt.h: what the last frame-march launch of the calling thread (vrt_render_tile, vrt_trace_rays;
+// not the re-traces, not the batched kernels) kept in LDS and which kernel it ran -- the words of PlanRecord, up to n of them.
+// Host memory only: no device call, no synchronisation, legal during stream capture.  Returns the number of words there are.
+int vrt_diag_last_plan(int64_t* out, int n) {
+    if (!out || n < 0) return VRT_ERR_ARG;
+    for (int j = 0; j < n && j < VRT_PLAN_WORDS; j++) out[j] = g_plan.w[j];
+    return VRT_PLAN_WORDS;
 }
 
 #ifdef VRT_DIAG

@@ -67,7 +67,27 @@ def sparse_scene(seed, res_max, chunk_size=8, dims=(6, 6, 6), fill=0.02):
     return ol.Scene(origin, dims, cs, present, res, ol.Scene.camera_grid(grid, origin, dims, cs, present, res), mats)
 
 
-def check_frame_march(cam, o, cs, which, lookahead=None, window=None, **kw):
+# LDS of a frame-march workgroup (tests/test_gpu_lds_room.py).  A CU has 160 KiB and the march kernels
+# are built for VRT_WAVES_PER_SIMD = 4 workgroups of 256 threads on it.  Static LDS per kernel from the compiler's resource
+# report of the shipped source, by whether the instance looks ahead across chunk borders (W: its per-axis offset tables are
+# part of the world-axis tables in dynamic LDS); tests/test_kernel_resources.py pins both on the CPU.
+BUDGET_LDS = 160 * 1024 // 4
+STATIC_LDS = {False: 8032, True: 4976}
+POOL_LDS = 4 * 18 * 8 * 48      # 4 waves x 18 words x 8 bytes x 48 parked rays
+
+
+def march_dyn_lds(n_materials, ct_cells, bitmap_words, wt_cells, pool):
+    """Dynamic LDS bytes of a frame-march launch, restated from the documented sizes: 64 bytes per material, 4 per chunk-table
+    cell kept in LDS, 4 per word of the settled bitmap, rounded up to 16; then (cells + 64) * 4 bytes per world-table axis
+    (wt_cells: the world's cells per axis, or None without the look-ahead); then the ray pools; then 16 bytes."""
+    n = 64 * n_materials + 4 * ct_cells + 4 * bitmap_words
+    n = (n + 15) // 16 * 16
+    if wt_cells is not None:
+        n += sum((int(c) + 64) * 4 for c in wt_cells)
+    return n + (POOL_LDS if pool else 0) + 16
+
+
+def check_frame_march(cam, o, cs, which, lookahead=None, window=None, expect_pool=None, **kw):
     """The same frame WITHOUT ray records: `want_rays` selects the recording march_kernel whatever VRT_POOL says, so this is
     the render that runs the frame kernel the fixture names -- march_pool_kernel under "pool" (asserted: its workgroups
     count themselves in stats[12]), march_kernel under "lanes".  Per-sample colours, fp32 means, event counters and the
@@ -75,10 +95,15 @@ def check_frame_march(cam, o, cs, which, lookahead=None, window=None, **kw):
     window: what the VRT_TRAV_WINDOW=2 leg below must have been able to do -- True: the traversed box is one that gets the
     32^3-cell bitmap window (every side of 32 cells and more) AND the oracle's list has chunks both inside that window
     (the settled bit) and outside it (the key read at every visit); False: the box is too small for a window.  The result
-    says which it was (`window`: the window's lowest cell, or None)."""
+    says which it was (`window`: the window's lowest cell, or None).
+    expect_pool: for scenes whose materials and tables leave the ray pools no room in LDS (tests/test_gpu_lds_room.py) -- False:
+    march_kernel runs although the leg asks for the pool; None: the leg's own rule."""
     r = cam.render(0, want_ray_rgba=True, **kw)
     groups = int(r.stats[12]) & 0xffffffff     # (bits 32+: the workgroups that took their rays as tiles)
-    assert (groups > 0) if which.startswith("pool") else (groups == 0), (which, groups)
+    if expect_pool is None:
+        expect_pool = which.startswith("pool")
+    assert not expect_pool or which.startswith("pool"), (which, expect_pool)
+    assert (groups > 0) if expect_pool else (groups == 0), (which, groups)
     if lookahead is not None:   # did the march step look ahead across chunk borders (march_step_w)?
         assert (int(r.stats[14]) > 0) == bool(lookahead), (lookahead, int(r.stats[14]))
     assert np.array_equal(r.rgba_f32.cpu().numpy(), o["pix_mean"].astype(np.float32))

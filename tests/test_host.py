@@ -26,6 +26,21 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert L.vrt_status_string(0) == b"ok"
 
 
+def test_last_plan_diagnostic_is_exported_and_checks_its_arguments():
+    """vrt_diag_last_plan (outside include/vrt.h: no ABI change) reads host memory only: callable without a GPU.  A null
+    pointer is VRT_ERR_ARG; before any launch every word reads 0; the return value is the number of words there are."""
+    L = nat.lib()
+    assert L.vrt_diag_last_plan is not None and "vrt_diag_last_plan" not in nat.EXPORTS
+    assert L.vrt_diag_last_plan(None, 8) == -1                                # VRT_ERR_ARG
+    buf = (C.c_int64 * 64)(*([-7] * 64))
+    n = L.vrt_diag_last_plan(buf, 64)
+    assert 10 <= n <= 64 and (n - 10) % 5 == 0
+    assert list(buf[:n]) == [0] * n and list(buf[n:]) == [-7] * (64 - n)      # nothing written past the words
+    assert L.vrt_diag_last_plan(buf, -1) == -1
+    plan = nat.last_plan()
+    assert plan["launches"] == 0 and plan["probes"] == [] and set(nat.PLAN_FIELDS) < set(plan)
+
+
 def test_struct_layouts_match_header():
     assert C.sizeof(nat.VrtSettings) == 128
     assert C.sizeof(nat.VrtCamera) == 64

@@ -83,3 +83,19 @@ def test_kernels_that_make_their_ray_records_keep_four_waves(report, name):
     r = report[name]
     assert r["VGPRs Spill"] == 0 and r["Occupancy [waves/SIMD]"] >= 4 and r["VGPRs"] <= 128 and r["AGPRs"] == 0, (RAYGEN_KERNELS[name], r)
     assert r["ScratchSize [bytes/lane]"] <= 64 and r["SGPRs Spill"] <= 112, (RAYGEN_KERNELS[name], r)
+
+
+def test_static_lds_of_the_frame_kernels(report):
+    """tests/test_gpu_lds_room.py places its scenes between byte thresholds that rest on the static LDS of the frame kernels
+    (gpu_util.STATIC_LDS): every march_kernel / march_pool_kernel instance has the one figure or the other, by whether it
+    looks ahead across chunk borders (the look-ahead variants keep their offset tables in dynamic LDS)."""
+    from gpu_util import STATIC_LDS
+    frame = {n: r for n, r in report.items() if re.match(r"_Z(12march_kernel|17march_pool_kernel)I", n)}
+    assert len(frame) >= len(FRAME_KERNELS) + len(RAYGEN_KERNELS)
+    for n, r in frame.items():
+        ahead = "variant" in FRAME_KERNELS.get(n, "") and "look-ahead" in FRAME_KERNELS[n]
+        if n not in FRAME_KERNELS:   # (march_pool_kernel<SPEC, RES, PERPIX, W, ...>, march_kernel<SPEC, RES, RECORD, LIST, LK, PERPIX, W, ...>)
+            args = re.findall(r"L[ib](\d+)E", n)
+            ahead = args[3 if "pool" in n else 6] == "1"
+        assert r["LDS Size [bytes/block]"] == STATIC_LDS[ahead], (n, r["LDS Size [bytes/block]"])
+    assert {STATIC_LDS[True], STATIC_LDS[False]} == {r["LDS Size [bytes/block]"] for r in frame.values()}
