@@ -146,6 +146,8 @@ enum { VRT_S_RAYS = 8, VRT_S_RNG_RETRACED = 9, VRT_S_RNG_EXHAUSTED = 10, VRT_S_T
                                         VRT_SCENE_LAYOUT_DENSE scenes) */
        VRT_S_RAYGEN_GROUPS = 15,  /* workgroups of the frame's march that worked out their rays' lens quaternions and lives
                                      themselves (vrt_render_tile without d_ray_table: no ray table is written then) */
+       VRT_S_CAST_REJECTED = 9,  /* vrt_cast_rays only (which re-traces nothing: the index is free there): rays the device
+                                    refused -- see vrt_cast_ray */
        VRT_NSTATS = 16 };
 
 int vrt_abi_version(void);
@@ -307,7 +309,7 @@ typedef struct vrt_hit {
     double  pos[3];    /* ray.pos at that moment */
     int32_t cell[3];   /* floor(pos): the voxel asked for (init.py:76) */
     int32_t material;  /* material id of the first voxel found (1..255), 0 = none within the ray's life, -1 = unused sample
-                          slot (every other field of such a record is 0) */
+                          slot, -2 = rejected ray of vrt_cast_rays (every other field of a -1 or -2 record is 0) */
 } vrt_hit;
 
 /* d_hits[k], k = p * max_samples + s, describes ray slot k of vrt_render_tile for the same pixel list, settings and camera.
@@ -334,6 +336,38 @@ int vrt_first_hit_views(const vrt_scene* scene, const vrt_settings* st, const vr
                         const int32_t* d_pixels_xy, int64_t n_px, const void* d_plan, int64_t n_distinct,
                         const double* d_ray_table, int32_t first_sample_only, void* d_workspace, int64_t workspace_bytes,
                         vrt_hit* d_hits, uint64_t* d_stats, void* stream);
+
+/* ---- explicit rays ------------------------------------------------------------------------------------
+ * The first voxel along rays that come from no camera: range sensors, line of sight between two points, a projectile's
+ * path, audio occlusion, a probe ahead of a moving box.  One launch marches n_rays rays, each from its own origin along its
+ * own velocity for its own life: the reference's loop (init.py:66-116) from exactly that state up to the first non-empty
+ * voxel, so every record is bit for bit what the renderer's ray would give from there.  The library does no arithmetic on
+ * origin and vel.  No camera, plan, ray table, draws, materials or workspace; no traversed list, no bounces, no material
+ * filter. */
+typedef struct vrt_cast_ray {   /* 64 bytes, 64-byte aligned array */
+    double origin[3];           /* ray.pos at step 0 */
+    double vel[3];              /* ray.vel: pos advances by vel * stepsize per step (init.py:114-116); any length */
+    double life;                /* the loop runs while step < life (init.py:66) */
+    double reserved;            /* ignored */
+} vrt_cast_ray;
+
+/* d_hits[k] describes d_rays[k] (both DEVICE arrays of n_rays records).
+ *   st        supplies chunk_size and chunk_radius (and is checked like every settings block); dist_min, dist_max and the
+ *             rest are not read.
+ *   max_life  in (0, 2^28]: the caller's bound on how long a lane may march.
+ *   d_stats   [VRT_NSTATS] uint64, zeroed by the callee: word 8 (VRT_S_RAYS) = rays marched, word 4 (VRT_C_HIT) = rays that
+ *             found a voxel, word 9 (VRT_S_CAST_REJECTED) = rays rejected, every other word 0 (while the call runs the
+ *             library keeps its launch-wide ray counter in the last word).
+ * The rays are device data and the call does not synchronise, so each ray is validated on the device.  A ray is REJECTED --
+ * not marched, material -2, every other field 0, counted -- when one of its seven doubles is not finite, when
+ * life > max_life, when |vel[a]| > 2^25 for an axis, or when it could leave the range the march's cell arithmetic covers:
+ *     |origin[a]| + (max(life, 0) + 2 * chunk_size + 2) * max(1, |vel|_inf) < 2^28    must hold for every axis a
+ * (vrt_render_tile's range rule, per ray).  A ray with life <= 0 is marched for no step: step 0, pos = origin, material 0.
+ * n_rays = 0 only zeroes the statistics; n_rays >= 2^32 is VRT_ERR_ARG; more than 2^28 rays are split into launches.
+ * Every argument is checked before any HIP call; nothing is allocated or synchronised, so a call may be captured into a
+ * hipGraph. */
+int vrt_cast_rays(const vrt_scene* scene, const vrt_settings* st, const vrt_cast_ray* d_rays, int64_t n_rays,
+                  double max_life, vrt_hit* d_hits, uint64_t* d_stats, void* stream);
 
 /* Camera.trace (init.py:37-121) for explicit rays: direction (dir_x, dir_y), detail and the random draws the
  * ray may consume (d_draws[i * n_draws + k] = k-th random.random() of ray i).  d_rays[i].counters[VRT_C_DRAW]

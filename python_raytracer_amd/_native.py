@@ -35,6 +35,7 @@ NSTATS = 16
 COUNTER_NAMES = ["lookup", "nbr", "resnap", "chunk_get", "hit", "draw", "adv", "broke"]
 S_RAYS, S_RNG_RETRACED, S_RNG_EXHAUSTED, S_TRAV_OUTSIDE, S_POOL_GROUPS, S_STALLED, S_LOOKAHEAD_GROUPS = 8, 9, 10, 11, 12, 13, 14
 S_RAYGEN_GROUPS = 15
+S_CAST_REJECTED = 9   # vrt_cast_rays only: rays the device refused (VRT_S_CAST_REJECTED)
 
 
 def needs_build():
@@ -100,6 +101,15 @@ class VrtHit(C.Structure):
 HIT_FIELDS = [("step", "<f8"), ("pos", "<f8", 3), ("cell", "<i4", 3), ("material", "<i4")]
 HIT_BYTES = 48
 
+
+class VrtCastRay(C.Structure):
+    """vrt_cast_ray (include/vrt.h): one explicit ray of vrt_cast_rays, 64 bytes."""
+    _fields_ = [("origin", C.c_double * 3), ("vel", C.c_double * 3), ("life", C.c_double), ("reserved", C.c_double)]
+
+
+CAST_RAY_BYTES = 64
+HIT_REJECTED = -2   # vrt_hit.material of a ray vrt_cast_rays refused
+
 _lib = None
 
 
@@ -152,6 +162,8 @@ def lib():
     L.vrt_first_hit_views.restype = C.c_int
     L.vrt_first_hit_views.argtypes = [C.POINTER(VrtScene), C.POINTER(VrtSettings), vp, i32, vp, i64, vp, i64, vp, i32, vp, i64,
                                       vp, vp, vp]
+    L.vrt_cast_rays.restype = C.c_int
+    L.vrt_cast_rays.argtypes = [C.POINTER(VrtScene), C.POINTER(VrtSettings), vp, i64, C.c_double, vp, vp, vp]
     L.vrt_draw_table_bytes.restype = C.c_int
     L.vrt_draw_table_bytes.argtypes = [i64, i32, C.POINTER(i64)]
     L.vrt_draw_table_build.restype = C.c_int
@@ -202,7 +214,7 @@ def lib():
 EXPORTS = ["vrt_abi_version", "vrt_status_string", "vrt_last_hip_error", "vrt_device_count", "vrt_release_caches", "vrt_voxel_offset",
            "vrt_max_samples", "vrt_plan_bytes", "vrt_plan_build", "vrt_workspace_bytes", "vrt_render_tile",
            "vrt_views_workspace_bytes", "vrt_render_views",
-           "vrt_first_hit", "vrt_first_hit_views_workspace_bytes", "vrt_first_hit_views",
+           "vrt_first_hit", "vrt_first_hit_views_workspace_bytes", "vrt_first_hit_views", "vrt_cast_rays",
            "vrt_draw_table_bytes", "vrt_draw_table_build", "vrt_ray_table_bytes", "vrt_ray_table_build",
            "vrt_pow_memo_create", "vrt_occupancy_build", "vrt_canvas_blit", "vrt_world_tables_bytes", "vrt_world_tables_build",
            "vrt_trace_workspace_bytes", "vrt_trace_rays", "vrt_rng_draws",

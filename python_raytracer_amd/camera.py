@@ -156,6 +156,45 @@ class HitResult:
         return self._scatter(self.material, -1, torch.int32)
 
 
+class CastResult:
+    """Device-side records of Camera.cast_rays: what every explicit ray found.  `step`, `pos`, `cell` and `material` are
+    views of one buffer of 48-byte vrt_hit records (include/vrt.h), record k for ray k."""
+
+    def __init__(self, records, stats_dev):
+        import torch
+        n = records.numel() // nat.HIT_BYTES
+        f64 = records.view(torch.float64).view(n, nat.HIT_BYTES // 8)
+        i32 = records.view(torch.int32).view(n, nat.HIT_BYTES // 4)
+        self.records = records           # uint8 [n * 48]
+        self.step = f64[:, 0]            # float64 [n]: ray.step at the first voxel, or >= the ray's life for a miss
+        self.pos = f64[:, 1:4]           # float64 [n, 3]: ray.pos at that moment
+        self.cell = i32[:, 8:11]         # int32 [n, 3]: floor(pos)
+        self.material = i32[:, 11]       # int32 [n]: 1..255 the material found, 0 none, -2 the ray was rejected
+        self._stats_dev = stats_dev
+        self._stats = None
+
+    @property
+    def stats(self):
+        """numpy int64[16], copied from the device on first use (a synchronisation): word 8 = rays marched, word 4 = rays
+        that found a voxel, word 9 = rays rejected."""
+        if self._stats is None:
+            self._stats = self._stats_dev.cpu().numpy()
+        return self._stats
+
+    def numpy(self):
+        """The records as a numpy structured array (fields step, pos, cell, material)."""
+        return self.records.cpu().numpy().view(np.dtype(nat.HIT_FIELDS))
+
+    def hit_mask(self):
+        """torch.bool [n]: the ray found a voxel within its life."""
+        return self.material > 0
+
+    def rejected_mask(self):
+        """torch.bool [n]: the ray was rejected on the device (not finite, life > max_life, |vel| > 2**25, or out of
+        range: include/vrt.h, vrt_cast_ray) and was not marched."""
+        return self.material == nat.HIT_REJECTED
+
+
 class Camera:
     def __init__(self, settings=None, device=None):
         import torch
@@ -917,6 +956,143 @@ class Camera:
             nat.check(rc, "vrt_first_hit_views")
         return [HitResult(records[v * per_view:(v + 1) * per_view], dp.array, samples, smax, int(s.height), int(s.width), stats)
                 for v in range(n_views)]
+
+    # ------------------------------------------------------------------ explicit rays: the first voxel along any ray
+    def _cast_records(self, origins, velocities, lives, default_life):
+        """[n, 8] float64 device tensor of vrt_cast_ray records from what cast_rays was given."""
+        torch = self._torch
+        dev = self._require_device()
+
+        def is_t(v):
+            return isinstance(v, torch.Tensor)
+
+        if velocities is None:
+            # ready records, used as they are
+            if not is_t(origins) or origins.dtype != torch.float64 or not origins.is_cuda:
+                raise ValueError("cast_rays(records): the records must be one float64 CUDA tensor [n, 8]")
+            if origins.dim() != 2 or origins.shape[1] != 8 or not origins.is_contiguous() or origins.data_ptr() % 64:
+                raise ValueError("cast_rays(records): the records must be a contiguous, 64-byte aligned [n, 8] tensor")
+            if origins.device != dev:
+                raise ValueError("cast_rays(records): the records are on %s, the camera renders on %s" % (origins.device, dev))
+            if lives is not None:
+                raise ValueError("cast_rays(records): ready records carry their own lives")
+            return origins
+        parts = []
+        for name, v in (("origins", origins), ("velocities", velocities)):
+            if is_t(v):
+                if not v.dtype.is_floating_point:
+                    raise ValueError("cast_rays: %s must be floating point, not %s" % (name, v.dtype))
+                v = v.to(device=dev, dtype=torch.float64)
+            else:
+                a = np.asarray(v)
+                if a.dtype.kind not in "fiu":
+                    raise ValueError("cast_rays: %s must be numbers, not %s" % (name, a.dtype))
+                v = torch.from_numpy(np.array(a, np.float64)).to(dev)
+            if v.dim() != 2 or v.shape[1] != 3:
+                raise ValueError("cast_rays: %s must have shape [n, 3], not %s" % (name, list(v.shape)))
+            parts.append(v)
+        n = int(parts[0].shape[0])
+        if int(parts[1].shape[0]) != n:
+            raise ValueError("cast_rays: %d origins but %d velocities" % (n, int(parts[1].shape[0])))
+        rec = torch.zeros((n, 8), dtype=torch.float64, device=dev)
+        rec[:, 0:3] = parts[0]
+        rec[:, 3:6] = parts[1]
+        if lives is None:
+            rec[:, 6] = float(default_life)
+        else:
+            lv = lives.to(device=dev, dtype=torch.float64) if is_t(lives) else \
+                torch.from_numpy(np.array(lives, np.float64)).to(dev)
+            if lv.dim() != 1 or int(lv.shape[0]) != n:
+                raise ValueError("cast_rays: lives must have shape [%d], not %s" % (n, list(lv.shape)))
+            rec[:, 6] = lv
+        return rec
+
+    def cast_rays(self, origins, velocities=None, lives=None, max_life=None, stream=None):
+        """The first voxel along explicit rays (vrt_cast_rays): ray k starts at origins[k], advances by velocities[k] per
+        unit of step and lives for lives[k] -- the reference's loop (init.py:66-116) from exactly that state up to the first
+        non-empty voxel, bit for bit what the renderer's ray would do from there.  The rays go against the scene this
+        camera currently renders (the packed scene of first_hit(), LODs included).  No traversed list, no bounces, no
+        material filter.
+        origins, velocities: [n, 3], numpy or torch; or pass ONE [n, 8] float64 CUDA tensor of ready vrt_cast_ray records
+        (origin, vel, life, reserved), which is used without a copy.  lives: [n], default dist_max - dist_min.
+        max_life: the bound on how long a lane may march, default settings.dist_max.
+        A ray is REJECTED on the device -- material -2, every other field 0, counted in stats[9] -- when a value is not
+        finite, when life > max_life, when |vel| > 2**25 on an axis, or unless
+        |origin| + (max(life, 0) + 2 * chunk_size + 2) * max(1, |vel|_inf) < 2**28 on every axis.
+        Returns a CastResult of device tensors; nothing is copied to the host and nothing synchronises (with tensors
+        already on the device the call can be captured into a graph)."""
+        torch = self._torch
+        L = nat.lib()
+        dev = self._require_device()
+        s = self._settings()
+        if max_life is None:
+            max_life = float(s.dist_max)
+        max_life = float(max_life)
+        if not (max_life > 0) or max_life > float(1 << 28):
+            raise ValueError("cast_rays: max_life must lie in (0, 2**28], not %r" % max_life)
+        sc = self._ensure_scene()
+        st = self._c_settings(0)
+        with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            rec = self._cast_records(origins, velocities, lives, float(s.dist_max) - float(s.dist_min))
+            n = int(rec.shape[0])
+            if n == 0:
+                raise ValueError("cast_rays: no rays")
+            if n >= 1 << 32:
+                raise ValueError("cast_rays: 2**32 rays and more need several calls")
+            csc = self._c_scene(sc)
+            records = torch.empty(n * nat.HIT_BYTES, dtype=torch.uint8, device=dev)
+            stats = torch.empty(nat.NSTATS, dtype=torch.int64, device=dev)   # (the library clears it)
+            rc = L.vrt_cast_rays(C.byref(csc), C.byref(st), rec.data_ptr(), n, max_life, records.data_ptr(), stats.data_ptr(),
+                                 torch.cuda.current_stream().cuda_stream)
+            nat.check(rc, "vrt_cast_rays")
+        return CastResult(records, stats)
+
+    def line_of_sight(self, a, b, stream=None):
+        """torch.bool [n]: can point a[k] see point b[k]?  One cast per pair: vel = (b - a) / max|b - a| -- the reference's
+        Chebyshev normalize (lib.py:310-314), left as it is where the maximum is 0 or 1 -- and life = max|b - a|; true
+        where that ray found no voxel.  This is the renderer's own sampling: unit steps along the dominant axis, one voxel
+        looked up per step (larger steps through coarser and empty chunks), so a thin diagonal gap is open or closed
+        exactly as it is in the image, and a voxel at b itself (a step the life no longer covers) does not block.
+        Raises ValueError when the cast rejected a pair (see cast_rays); that check synchronises."""
+        torch = self._torch
+        dev = self._require_device()
+
+        def pts(name, v):
+            if isinstance(v, torch.Tensor):
+                if not v.dtype.is_floating_point:
+                    raise ValueError("line_of_sight: %s must be floating point, not %s" % (name, v.dtype))
+                v = v.to(device=dev, dtype=torch.float64)
+            else:
+                arr = np.asarray(v)
+                if arr.dtype.kind not in "fiu":
+                    raise ValueError("line_of_sight: %s must be numbers, not %s" % (name, arr.dtype))
+                v = torch.from_numpy(np.array(arr, np.float64)).to(dev)
+            if v.dim() != 2 or v.shape[1] != 3:
+                raise ValueError("line_of_sight: %s must have shape [n, 3], not %s" % (name, list(v.shape)))
+            return v
+
+        with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            pa, pb = pts("a", a), pts("b", b)
+            if pa.shape != pb.shape:
+                raise ValueError("line_of_sight: %d points a but %d points b" % (int(pa.shape[0]), int(pb.shape[0])))
+            if int(pa.shape[0]) == 0:
+                raise ValueError("line_of_sight: no pairs")
+            d = pb - pa
+            ref = d.abs().amax(dim=1)
+            keep = (ref == 0) | (ref == 1)            # lib.py:312: `if ref and ref != 1`
+            vel = torch.where(keep[:, None], d, d / torch.where(keep, torch.ones_like(ref), ref)[:, None])
+            rec = torch.zeros((int(pa.shape[0]), 8), dtype=torch.float64, device=dev)
+            rec[:, 0:3] = pa
+            rec[:, 3:6] = vel
+            rec[:, 6] = ref
+            # (the bound on a lane's march follows the longest pair, not dist_max; a pair that is not finite is rejected below)
+            bound = float(torch.where(torch.isfinite(ref), ref, torch.zeros_like(ref)).max())
+            res = self.cast_rays(rec, max_life=min(max(bound, 1.0), float(1 << 28)), stream=stream)
+            bad = res.rejected_mask()
+            if bool(bad.any()):
+                raise ValueError("line_of_sight: %d of %d pairs were rejected (not finite, or out of the range "
+                                 "|a| + (max|b - a| + 2 * chunk_size + 2) < 2**28)" % (int(bad.sum()), int(bad.numel())))
+        return res.material == 0
 
     def tile(self, thread, t=0):
         """Reference signature and return triple (init.py:126-150): RGBA8 bytes of the full window (pixels of other

@@ -3076,6 +3076,162 @@ __global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) first_hit_kerne
     }
 }
 
+// ---- cast_kernel: the first voxel along explicit rays (vrt_cast_rays) ----------------------------------------------------
+// first_hit_kernel's sibling for rays that come from no camera: record k of the launch is ray k of the caller's array, a
+// 64-byte vrt_cast_ray whose origin, velocity and life ARE the state of init.py:50-59 -- the lane copies them, it computes
+// nothing from them -- so from there on the ray is the renderer's ray from that state: the same march_step, the same
+// write_hit.  The hand-out, the lane set-up, the chunk table in dynamic LDS and the offset tables are first_hit_kernel's; no
+// camera is staged (COLD_POS, COLD_ROT and COLD_DIST_MIN stay 0 and nothing reads them).
+// The rays are device data and the call does not synchronise, so every ray is validated here (cast_ray_ok): a rejected ray
+// is not marched, gets material -2 and is counted in stats[VRT_S_CAST_REJECTED].  MarchParams carries the rays where a
+// first-hit launch carries its ray table (tab.rec: both records are 64 bytes) and the caller's bound on a ray's life in `lens`.
+struct __align__(16) CastRecord {  // vrt_cast_ray as the lane fetches it: four 16-byte loads, one round trip
+    double ox, oy, oz;
+    double vx, vy, vz;
+    double life, reserved;
+};
+static_assert(sizeof(CastRecord) == sizeof(vrt_cast_ray) && sizeof(CastRecord) == sizeof(RayRecord), "cast record is 64 bytes");
+// The frame's range rule (fill_params) per ray: everything finite, the life within the caller's bound, and every position
+// the ray can reach -- its life, one void-skip step and the look-ahead's margin at its own speed -- inside +-2^28, where the
+// march's 32-bit cell arithmetic holds.  (!(x < y) is true for a NaN: no separate test for one.)
+__device__ __forceinline__ bool cast_ray_ok(const CastRecord& c, double max_life, double cs) {
+    const double vmax = __builtin_fmax(__builtin_fmax(__builtin_fabs(c.vx), __builtin_fabs(c.vy)), __builtin_fabs(c.vz));
+    const double omax = __builtin_fmax(__builtin_fmax(__builtin_fabs(c.ox), __builtin_fabs(c.oy)), __builtin_fabs(c.oz));
+    // (fmax drops a NaN operand, so finiteness is asked separately: x * 0 is 0 for a finite x and NaN otherwise, and a sum
+    // of finite values that overflows is rejected like the infinity it is)
+    const double nf = (c.ox + c.oy + c.oz) * 0.0 + (c.vx + c.vy + c.vz) * 0.0 + c.life * 0.0;
+    if (!(nf == 0.0)) return false;
+    if (!(c.life <= max_life) || !(vmax <= 0x1p25)) return false;
+    const double reach = ((c.life > 0.0 ? c.life : 0.0) + 2.0 * cs + 2.0) * (vmax > 1.0 ? vmax : 1.0);
+    return omax + reach < 0x1p28;
+}
+template <int SPEC, int RESMODE>
+__global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) cast_kernel(MarchParams P) {
+    static_assert(SPEC >= 4 && SPEC <= 16, "speculation depth");
+    __shared__ FirstHitShared S;
+    extern __shared__ __align__(16) unsigned char s_dyn[];
+    MarchCtx C;
+    {
+        uint32_t* s_ct = reinterpret_cast<uint32_t*>(s_dyn);
+        for (int i = threadIdx.x; i < P.ct_cells; i += VRT_BLOCK) s_ct[i] = P.chunk_table[i];
+        for (int i = threadIdx.x; i < 256; i += VRT_BLOCK) {
+            const int c = i < P.cs ? i : 0;  // (entries beyond the chunk are never selected)
+            S.tab[i] = (uint32_t)voxel_offset(P.cs, c, 0, 0);
+            S.tab[256 + i] = (uint32_t)voxel_offset(P.cs, 0, c, 0);
+            S.tab[512 + i] = (uint32_t)voxel_offset(P.cs, 0, 0, c);
+        }
+        if (threadIdx.x == 0) {
+            for (int j = 0; j < COLD_N; j++) S.cold[j] = 0.0;
+            S.cold[COLD_CS] = (double)P.cs;
+            S.cold[COLD_INV_CS] = 1.0 / (double)P.cs;
+        }
+        C.vw = nullptr;
+        C.tab = (const lds_char*)S.tab;
+        C.tl[0] = 0;
+        C.tl[1] = 1024;
+        C.tl[2] = 2048;
+        C.ct = (const lds_u32*)s_ct;
+        C.bm = nullptr;
+        C.mats = nullptr;
+        C.cold = (const lds_f64*)S.cold;
+        C.tot = nullptr;
+        C.pc.keys = C.pc.vals = C.pc.gkeys = C.pc.gvals = nullptr;
+        C.vox = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(P.voxels), 0, (int)P.vox_bytes, 0x00020000);
+        C.cs4 = (unsigned)P.cs << 2;
+        C.cs = (double)P.cs;
+        C.inv_cs = 1.0 / C.cs;
+        C.kept_cs = true;
+        C.has_bm = false;
+        C.tile = true;
+        C.wt = nullptr;
+        C.cs3 = 1u << (3 * P.cs_shift);
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            C.td[a] = C.toc[a] = C.wb[a] = 0;
+            C.oc[a] = P.origin_c[a];
+            C.dm[a] = P.dims[a];
+        }
+    }
+    __syncthreads();
+
+    HandOut H;  // (of rays = records)
+    H.init(P.n, P.chunk);
+
+    Ray r;
+    ray_clear(r);
+    uint32_t rec = 0;        // the lane's ray and its record
+    int state = LANE_IDLE;
+    uint32_t n_rays = 0, n_found = 0, n_bad = 0;  // wave-uniform: rays marched / that found a voxel / rejected
+    // what the shared bodies take besides the ray and the pass has no use for (all of it dead code here)
+    int32_t cnt[C_NLOCAL];
+#pragma unroll
+    for (int j = 0; j < C_NLOCAL; j++) cnt[j] = 0;
+    SeenList<false> sl = seen_unused();
+    LkState lk = lk_unused();
+    DG_LANE(dg);
+
+    for (;;) {
+        // ------------------------------------------------------------------ refill idle lanes
+        unsigned long long idle_mask = __ballot(state == LANE_IDLE);
+        while (idle_mask != 0ull && H.left()) {
+            if (H.used_up()) {
+                H.take_chunk(P.queue_head);
+                if (!H.more) break;
+            }
+            const int64_t k = H.hand(idle_mask);
+            bool bad = false;
+            if (state == LANE_IDLE && k < H.range_end) {
+                const auto& Q = fresh_args(P);
+                rec = (uint32_t)k;
+                // the whole record is fetched at once (one memory round trip), then inspected
+                const CastRecord c = reinterpret_cast<const CastRecord*>(Q.tab.rec)[rec];
+                if (cast_ray_ok(c, Q.lens, C.cs)) {
+                    // init.py:50-59: the caller's doubles are the ray's state
+                    r.px = c.ox; r.py = c.oy; r.pz = c.oz;
+                    r.vx = c.vx; r.vy = c.vy; r.vz = c.vz;
+                    r.life = c.life;
+                    r.step = 0;
+                    r.bounces = 0;
+                    r.energy = 0;
+                    r.color = 0;
+                    // chunk_min = chunk_max = vec3(0, 0, 0), chunk = None (init.py:46-47): see take_ray
+                    r.nm4x = r.nm4y = r.nm4z = (int)0x80000000u;
+                    r.entry = 0;
+                    r.boff = 0;
+                    r.resnaps = 0;
+                    state = LANE_MARCH;
+                } else {
+                    write_hit(Q.hits + rec, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, -2);  // rejected: reported, never marched
+                    bad = true;
+                }
+            }
+            n_bad += (uint32_t)__popcll(__ballot(bad));
+            idle_mask = __ballot(state == LANE_IDLE);
+        }
+        if (__ballot(state != LANE_IDLE) == 0ull) break;  // range exhausted and every lane finished
+
+        // ------------------------------------------------------------------ MARCH steps, until a lane is done
+        while (__ballot(state > LANE_MARCH) == 0ull) {
+            if (state == LANE_MARCH) march_step<SPEC, RESMODE, false, 0, VRT_FRESH_MARCH, 0, 3>(P, C, r, state, cnt, 0ull, lk, sl, dg);
+        }
+
+        // ------------------------------------------------------------------ the record (LANE_HIT: the first voxel; LANE_ENDED: none)
+        n_rays += (uint32_t)__popcll(__ballot(state > LANE_MARCH));
+        n_found += (uint32_t)__popcll(__ballot(state == LANE_HIT));
+        if (state > LANE_MARCH) {
+            int cx, cy, cz;
+            floor3_i32(r.px, r.py, r.pz, cx, cy, cz);
+            write_hit(fresh_args(P).hits + rec, r.step, r.px, r.py, r.pz, cx, cy, cz, state == LANE_HIT ? (int)(r.color >> 24) : 0);
+            state = LANE_IDLE;
+        }
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (n_rays) atomicAdd((unsigned long long*)&P.stats[VRT_S_RAYS], (unsigned long long)n_rays);
+        if (n_found) atomicAdd((unsigned long long*)&P.stats[VRT_C_HIT], (unsigned long long)n_found);
+        if (n_bad) atomicAdd((unsigned long long*)&P.stats[VRT_S_CAST_REJECTED], (unsigned long long)n_bad);
+    }
+}
+
 // ---- march_pool_kernel: the same bodies, rays regrouped between the lanes of a wave through LDS ------------------------
 // march_kernel executes a body for the lanes that wait for it while the others idle: per VALU instruction 49 % of the
 // lanes are active at config 3 (profiles/r02_v7_sq_c3_summary.txt), and the kernel is bound by VALU issue.  Here every
@@ -4132,9 +4288,12 @@ int vrt_workspace_bytes(const vrt_settings* st, int64_t n_px, int64_t n_distinct
 
 static inline bool within(double v, double lim) { return __builtin_fabs(v) <= lim; }  // false for NaN
 
-static int fill_params(MarchParams& P, const vrt_scene* sc, const vrt_settings* st, const vrt_camera* cam,
-                       const vrt_traversed* trav, uint64_t* d_stats) {
-    if (!sc || !cam || check_settings(st) != VRT_OK) return VRT_ERR_ARG;
+// The scene half of a launch's parameters, and the camera half where there is a camera: `cam` is NULL for vrt_cast_rays,
+// whose rays come from no camera -- their range is checked ray by ray on the device (cast_ray_ok) -- and which records no
+// traversed list.
+static int fill_scene_params(MarchParams& P, const vrt_scene* sc, const vrt_settings* st, const vrt_camera* cam,
+                             const vrt_traversed* trav, uint64_t* d_stats) {
+    if (!sc || check_settings(st) != VRT_OK || (!cam && trav)) return VRT_ERR_ARG;
     if (sc->chunk_size != st->chunk_size || sc->n_materials < 0 || sc->n_materials > 255) return VRT_ERR_ARG;
     if (!sc->d_chunk_table || (sc->n_slots > 0 && !sc->d_voxels) || (sc->n_materials > 0 && !sc->d_materials))
         return VRT_ERR_ARG;
@@ -4145,7 +4304,7 @@ static int fill_params(MarchParams& P, const vrt_scene* sc, const vrt_settings* 
     // The march keeps 4 * floor(pos) in 32-bit integers: the camera and everything a ray can reach must stay inside
     // +-2^28.  |vel|_inf <= 8 |rot|^2 + 1 for the reference's (not norm-preserving) quaternion product applied to a
     // unit lens quaternion (lib.py:353-358, 372-376); a ray travels at most dist_max - dist_min plus one void-skip step.
-    {
+    if (cam) {
         double q2 = 0;
         for (int a = 0; a < 4; a++) {
             if (!within(cam->rot[a], 1e3)) return VRT_ERR_ARG;
@@ -4158,7 +4317,8 @@ static int fill_params(MarchParams& P, const vrt_scene* sc, const vrt_settings* 
             if (!(__builtin_fabs(cam->pos[a]) + reach < 0x1p28)) return VRT_ERR_ARG;
     }
     P.st = *st;
-    P.cam = *cam;
+    if (cam) P.cam = *cam;
+    else P.cam = vrt_camera{};
     int shift = 0;
     while ((1 << shift) < st->chunk_size) shift++;
     P.cs = st->chunk_size;
@@ -4283,6 +4443,11 @@ static int fill_params(MarchParams& P, const vrt_scene* sc, const vrt_settings* 
     P.lens = 0.0;
     march_policy(march_big_scene(sc), 0, P.t_hit, P.t_end, P.max_iters);  // the launch sites set it for their ray count
     return VRT_OK;
+}
+static int fill_params(MarchParams& P, const vrt_scene* sc, const vrt_settings* st, const vrt_camera* cam,
+                       const vrt_traversed* trav, uint64_t* d_stats) {
+    if (!cam) return VRT_ERR_ARG;
+    return fill_scene_params(P, sc, st, cam, trav, d_stats);
 }
 
 }  // extern "C"
@@ -5218,6 +5383,50 @@ int vrt_first_hit_views(const vrt_scene* scene, const vrt_settings* st, const vr
         {
             ProfScope ps(stream, VRT_PROF_MARCH);
             launch_first_hit<true>(P, march_grid(n), resmode, nv, stream);
+        }
+        clear_words(d_stats + VRT_NSTATS - 1, 8, stream);
+    }
+    HIP_TRY(hipGetLastError());
+    return VRT_OK;
+}
+
+// ---- explicit rays (vrt_cast_rays) ---------------------------------------------------------------------------------------
+}  // extern "C"
+
+// kernel variant: as launch_first_hit chooses it (resolution mode from vrt_scene.max_resolution)
+static void launch_cast(MarchParams P, int grid, int resmode, hipStream_t stream) {
+    const size_t lds = first_hit_lds(P, 0);  // the chunk table, if it fits
+    if (resmode == 0) hipLaunchKernelGGL((cast_kernel<VRT_SPEC_DEEP, 0>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
+    else if (resmode == 1) hipLaunchKernelGGL((cast_kernel<VRT_SPEC_DEEP, 1>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
+    else hipLaunchKernelGGL((cast_kernel<VRT_SPEC, 2>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
+}
+
+extern "C" {
+
+int vrt_cast_rays(const vrt_scene* scene, const vrt_settings* st, const vrt_cast_ray* d_rays, int64_t n_rays, double max_life,
+                  vrt_hit* d_hits, uint64_t* d_stats, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    MarchParams P;
+    int rc = fill_scene_params(P, scene, st, nullptr, nullptr, d_stats);  // (every check comes before any HIP call)
+    if (rc != VRT_OK) return rc;
+    if (n_rays < 0 || n_rays >= (1ll << 32) || !(max_life > 0.0) || !(max_life <= 0x1p28)) return VRT_ERR_ARG;
+    if (n_rays > 0 && (!d_rays || !d_hits || ((uintptr_t)d_rays & 63) != 0)) return VRT_ERR_ARG;
+    frame_begin(d_stats, nullptr, 0, nullptr, 0, nullptr, stream);
+    const int resmode = res_mode(scene);
+    P.lens = max_life;  // (cast_kernel: the bound on a ray's life)
+    P.ray0 = 0;
+    P.slot_stride = 1;
+    P.queue_head = (unsigned long long*)(d_stats + VRT_NSTATS - 1);  // (see vrt_first_hit)
+    const int64_t per_launch = batch_rays();
+    for (int64_t r0 = 0; r0 < n_rays; r0 += per_launch) {
+        const int64_t n = n_rays - r0 < per_launch ? n_rays - r0 : per_launch;
+        P.n = n;
+        P.chunk = march_chunk(n);
+        P.tab.rec = reinterpret_cast<RayRecord*>(const_cast<vrt_cast_ray*>(d_rays + r0));
+        P.hits = d_hits + r0;
+        {
+            ProfScope ps(stream, VRT_PROF_MARCH);
+            launch_cast(P, march_grid(n), resmode, stream);
         }
         clear_words(d_stats + VRT_NSTATS - 1, 8, stream);
     }

@@ -1,0 +1,391 @@
+"""Explicit rays (Camera.cast_rays / line_of_sight -> vrt_cast_rays, cast_kernel): the first voxel along any origin and
+velocity, bit for bit against the CPU oracle where the oracle can express the ray (tests/cast_ref.py: one 2 x 2 frame per
+ray), and against the Python restatement of the reference's loop -- pinned to the oracle in tests/test_cast_host.py --
+where it cannot.  Every oracle comparison is asserted not to be vacuous when its ray set is made (cast_ref.ray_set)."""
+import ctypes as C
+import hashlib
+
+import numpy as np
+import pytest
+
+import cast_ref as cr
+import oracle_lib as ol
+from gpu_util import HANDOUT_KNOBS, camera_for, run_children, settings_store
+from python_raytracer_amd import _native as nat
+
+gpu = pytest.mark.gpu
+
+IDENTITY = (0.0, 0.0, 0.0, 1.0)
+HIT_DTYPE = cr.HIT_DTYPE
+_cams = {}
+
+
+def scene_of(name):
+    return {"default": ol.default_scene, "synth64": ol.synth64_scene}[name]() if name in ("default", "synth64") else cr.ray_set(name)[0]
+
+
+def cam_of(name):
+    """A camera over the named scene with id-materials (its own pose plays no part in a cast)."""
+    key = {"default_scaled": "default", "default_dmin": "default"}.get(name, name)
+    if key not in _cams:
+        sc = scene_of(key)
+        st = ol.make_settings(width=32, height=24, samples=4, chunk_size=sc.chunk_size, dist_max=64)
+        _cams[key] = (camera_for(cr.id_scene(sc), settings_store(st), (0.0, 0.0, 0.0), IDENTITY, st["fov"] * np.pi / 8,
+                                 grid=getattr(sc, "grid_lod0", None)), sc)
+    return _cams[key]
+
+
+def check_stats(stats, exp):
+    n_bad = int((exp["material"] == -2).sum())
+    assert int(stats[8]) == len(exp) - n_bad and int(stats[4]) == int((exp["material"] > 0).sum()) and int(stats[9]) == n_bad, stats
+    assert (np.delete(stats, [4, 8, 9]) == 0).all(), stats
+
+
+def check_set(name):
+    cam, _ = cam_of(name)
+    sc, origins, vels, lives, exp = cr.ray_set(name)
+    res = cam.cast_rays(origins, vels, lives)
+    cr.assert_records_equal(res.numpy(), exp)
+    check_stats(res.stats, exp)
+    assert np.array_equal(res.hit_mask().cpu().numpy(), exp["material"] > 0) and not res.rejected_mask().any()
+    return cam, res
+
+
+def check_restated(name, origins, vels, lives, **kw):
+    cam, sc = cam_of(name)
+    origins, vels, lives = (np.asarray(a, np.float64) for a in (origins, vels, lives))
+    exp = cr.march_records(sc, round(sc.chunk_size / 2), origins, vels, lives)
+    res = cam.cast_rays(origins, vels, lives, **kw)
+    cr.assert_records_equal(res.numpy(), exp)
+    check_stats(res.stats, exp)
+    return exp
+
+
+# ---- 1. oracle parity ------------------------------------------------------------------------------------------------
+@gpu
+@pytest.mark.parametrize("name", ["default", "synth64", "default_scaled", "default_dmin"])
+def test_against_the_oracle(name):
+    """The default scene (resolutions 1 and 2, missing chunks) and synth64 (an identity table: entries computed, not read),
+    1 500 rays each; then the default scene with quaternions of norm 0.5 .. 1.5 (|vel|_inf 0.18 .. 3.07) and with dist_min = 3."""
+    cam, res = check_set(name)
+    c = cam._c_scene(cam._ensure_scene())
+    if name == "synth64":
+        assert int(c.max_resolution) == 1 and (int(c.flags) & nat.SCENE_TABLE_IS_IDENTITY)
+    else:
+        assert int(c.max_resolution) == 2
+
+
+# ---- 2. generic resolution, void skipping, table from memory ---------------------------------------------------------
+@gpu
+@pytest.mark.parametrize("name", ["hand", "big_table"])
+def test_generic_resolution_and_table_from_memory(name):
+    cam, res = check_set(name)
+    c = cam._c_scene(cam._ensure_scene())
+    if name == "hand":
+        assert int(c.max_resolution) == 3
+    else:
+        assert int(np.prod(cr.ray_set(name)[0].dims)) == 4352 > 4096 and not (int(c.flags) & nat.SCENE_TABLE_IS_IDENTITY)
+
+
+# ---- 3. arbitrary velocities -----------------------------------------------------------------------------------------
+def filled_voxels(sc, n, rng):
+    """n voxels of the camera grid that hold a material, in chunks of resolution 1, as world coordinates."""
+    cs = sc.chunk_size
+    idx = np.argwhere(sc.grid > 0)
+    idx = idx[sc.res[tuple((idx // cs).T)] == 1]
+    return idx[rng.choice(len(idx), n, replace=False)] + sc.origin
+
+
+@gpu
+@pytest.mark.parametrize("name", ["synth64", "default"])
+def test_arbitrary_velocities_against_the_restatement(name):
+    cam, sc = cam_of(name)
+    cs = sc.chunk_size
+    rng = np.random.default_rng(11)
+    o, v, l = [], [], []
+
+    def add(origin, vel, life):
+        o.append(origin), v.append(vel), l.append(life)
+
+    # axis-aligned velocities from integer origins: every position is an integer, and every cs-th one lies exactly on a
+    # chunk face (the reference's inclusive box keeps the old chunk there)
+    for axis in range(3):
+        for sign in (1.0, -1.0):
+            for start in rng.integers(-40, 40, (6, 3)):
+                vel = [0.0, 0.0, 0.0]
+                vel[axis] = sign
+                add(start.astype(float), vel, 64.0)
+                add((start // cs * cs).astype(float), vel, 64.0)          # ... starting on a chunk corner
+    # Chebyshev-normalised directions (what line_of_sight and a reflected ray use), some with zero and -0.0 components
+    for k in range(150):
+        d = rng.normal(size=3)
+        d = d / np.abs(d).max()
+        if k % 5 == 0:
+            d[rng.integers(3)] = 0.0
+        if k % 5 == 1:
+            d[rng.integers(3)] = -0.0
+        add(rng.uniform(-40, 40, 3), d, rng.uniform(4, 64))
+    # velocities of any length
+    for k in range(60):
+        add(rng.uniform(-40, 40, 3), rng.normal(size=3) * rng.choice([0.05, 0.5, 2.0, 7.0]), rng.uniform(4, 64))
+    # no velocity at all: inside a voxel, in an empty cell and outside the scene
+    filled = filled_voxels(sc, 24, rng)
+    add(filled[0] + 0.5, [0.0, 0.0, 0.0], 5.0)
+    add(rng.uniform(-30, 30, 3), [0.0, -0.0, 0.0], 5.0)
+    add([500.5, 3.25, -7.0], [0.0, 0.0, 0.0], 40.0)
+    # the origin exactly (0, 0, 0): the one position the box before the first snap, (0, 0, 0) .. (0, 0, 0), holds
+    add([0.0, 0.0, 0.0], [1.0, 0.5, 0.25], 64.0)
+    add([0.0, 0.0, 0.0], [0.0, 0.0, 0.0], 20.0)
+    add([0.0, -0.0, 0.0], [-0.3, -1.0, 0.2], 64.0)
+    # origins inside a filled voxel: the hit is at step 0
+    for f in filled[1:]:
+        add(f + rng.uniform(0, 1, 3), rng.normal(size=3), 32.0)
+    # lives of 0, -1 and 0.5
+    for life in (0.0, -1.0, 0.5, -0.0):
+        add(filled[1] + 0.5, [1.0, 0.0, 0.0], life)
+        add(rng.uniform(-30, 30, 3), [0.5, 1.0, -0.25], life)
+    # one wave mixing lives 0.5 and 64
+    for k in range(64):
+        d = rng.normal(size=3)
+        add(rng.uniform(-40, 40, 3), d / np.abs(d).max(), 0.5 if k % 2 else 64.0)
+    exp = check_restated(name, o, v, l)
+    hit = exp["material"] > 0
+    assert 0.1 < hit.mean() < 0.9 and (exp["step"][hit] == 0).sum() >= 23
+    never = np.array(l) <= 0      # the loop does not run: step 0, pos = origin, material 0, counted as marched
+    assert (exp["step"][never] == 0).all() and (exp["material"][never] == 0).all()
+    assert np.array_equal(exp["pos"][never].view(np.uint64), np.array(o, np.float64)[never].view(np.uint64))
+
+
+# ---- 4. sizes and order ----------------------------------------------------------------------------------------------
+def two_thousand():
+    a, b = cr.ray_set("default"), cr.ray_set("default_scaled")
+    return [np.concatenate([x, y]) for x, y in zip(a[1:], b[1:])]
+
+
+@gpu
+def test_sizes_and_order():
+    import torch
+    cam, _ = cam_of("default")
+    origins, vels, lives, exp = two_thousand()
+    for n in (1, 63, 64, 65, 1999):
+        res = cam.cast_rays(origins[:n], vels[:n], lives[:n])
+        cr.assert_records_equal(res.numpy(), exp[:n])
+        check_stats(res.stats, exp[:n])
+    perm = np.random.default_rng(12).permutation(1999)
+    res = cam.cast_rays(origins[perm], vels[perm], lives[perm])
+    cr.assert_records_equal(res.numpy(), exp[perm])
+    # torch tensors and ready records give the same
+    rec = np.zeros((1999, 8))
+    rec[:, 0:3], rec[:, 3:6], rec[:, 6], rec[:, 7] = origins[:1999], vels[:1999], lives[:1999], 123.0
+    drec = torch.from_numpy(rec).cuda()
+    cr.assert_records_equal(cam.cast_rays(drec).numpy(), exp[:1999])
+    cr.assert_records_equal(cam.cast_rays(torch.from_numpy(origins[:70]), torch.from_numpy(vels[:70]).cuda(), lives[:70]).numpy(), exp[:70])
+    # n = 0: the statistics are zeroed and nothing else happens
+    stats = torch.full((nat.NSTATS,), 7, dtype=torch.int64, device="cuda")
+    st, csc = cam._c_settings(0), cam._c_scene(cam._ensure_scene())
+    assert nat.lib().vrt_cast_rays(C.byref(csc), C.byref(st), None, 0, 64.0, None, stats.data_ptr(), None) == 0
+    torch.cuda.synchronize()
+    assert (stats.cpu().numpy() == 0).all()
+    # the host-side checks
+    for bad in (lambda: cam.cast_rays(origins[:0], vels[:0]), lambda: cam.cast_rays(origins[:5], vels[:4]),
+                lambda: cam.cast_rays(origins[:5, :2], vels[:5]), lambda: cam.cast_rays(origins[:5], vels[:5], lives[:4]),
+                lambda: cam.cast_rays(origins[:5], vels[:5], max_life=0.0), lambda: cam.cast_rays(drec.float()),
+                lambda: cam.cast_rays(drec.cpu()), lambda: cam.cast_rays(drec[:, :7])):
+        with pytest.raises(ValueError):
+            bad()
+
+
+# ---- 5. the same rays as the camera ----------------------------------------------------------------------------------
+@gpu
+def test_same_rays_as_the_camera():
+    """The cached per-slot ray table read back (ox, oy, oz, ow, life); rot.multiply(o).vec_forward() and pos + vel * dist_min
+    formed in numpy in the reference's operation order (lib.py:353-358, 372-376; init.py:54); cast: the records are
+    Camera.first_hit(all_samples=True)'s at 32 x 24 x 4 on the raised default camera, for the used slots."""
+    from test_gpu_first_hit import case1
+    cam, st, h, exp = case1(False)
+    dp = cam._pixels_tensor(0, None)
+    tab = dp.ray_table.cpu().numpy().view(np.float64).reshape(-1, 8)[: len(exp)]
+    used = tab[:, 4] >= 0
+    assert np.array_equal(used, exp["material"] >= 0) and 0 < (~used).sum() < used.sum()
+    ox, oy, oz, ow = (tab[used, i] for i in range(4))
+    x, y, z, w = (float(v) for v in (cam.rot.x, cam.rot.y, cam.rot.z, cam.rot.w))
+    q = np.stack([w * ox + z * oy - y * oz + x * ow, z * ox + w * oy + x * oz + y * ow, y * ox - x * oy + w * oz + z * ow,
+                  x * ox - y * oy - z * oz + w * ow], -1)
+    vel = cr.vec_forward(q)
+    pos = np.array([float(cam.pos.x), float(cam.pos.y), float(cam.pos.z)])
+    origins = pos + vel * float(st["dist_min"])
+    res = cam.cast_rays(origins, vel, tab[used, 4], max_life=float(st["dist_max"]))
+    cr.assert_records_equal(res.numpy(), exp[used])
+    check_stats(res.stats, exp[used])
+    assert int(res.stats[8]) == int(h.stats[8]) and int(res.stats[4]) == int(h.stats[4])
+
+
+# ---- 6. rejection ----------------------------------------------------------------------------------------------------
+@gpu
+def test_bad_rays_are_rejected_and_reported():
+    cam, sc = cam_of("default")
+    origins, vels, lives, exp = (a[:200].copy() for a in cr.ray_set("default")[1:])
+    big = float(1 << 28)
+    nan, inf = float("nan"), float("inf")
+    bad = [([nan, 0, 0], [1, 0, 0], 10),                 # origin not finite
+           ([0, 0, 0], [0, inf, 0], 10),                 # velocity not finite
+           ([1, 2, 3], [1, 0, 0], 64.5),                 # life > max_life
+           ([0, big, 0], [0, 0, 1], 10),                 # origin at 2^28
+           ([1, 2, 3], [0, 0, -float(1 << 26)], 1),      # |vel| = 2^26
+           ([big - 90, 0, 0], [-1, 0.5, 0], 64),         # reach: 2^28 - 90 + (64 + 2 * 16 + 2) * 1 = 2^28 + 8
+           ([1, 2, 3], [1, 0, 0], nan),                  # life not finite
+           ([1, 2, 3], [0.5, -nan, 0], 10)]              # a NaN that fmax would drop
+    at = [0, 1, 63, 64, 100, 130, 199, 207]              # where the bad ones sit in the 208
+    o8, v8, l8, e8 = np.zeros((208, 3)), np.zeros((208, 3)), np.zeros(208), np.zeros(208, HIT_DTYPE)
+    good = np.setdiff1d(np.arange(208), at)
+    o8[good], v8[good], l8[good], e8[good] = origins, vels, lives, exp
+    for i, (bo, bv, bl) in zip(at, bad):
+        o8[i], v8[i], l8[i] = bo, bv, bl
+        e8["material"][i] = -2
+    res = cam.cast_rays(o8, v8, l8, max_life=64.0)
+    got = res.numpy()
+    cr.assert_records_equal(got, e8)
+    assert int(res.stats[9]) == 8 and int(res.stats[8]) == 200
+    check_stats(res.stats, e8)
+    assert np.array_equal(np.nonzero(res.rejected_mask().cpu().numpy())[0], at)
+    # the good ones are what a run without the bad ones gives
+    cr.assert_records_equal(got[good], cam.cast_rays(origins, vels, lives, max_life=64.0).numpy())
+    # just inside the range rule: accepted, and marched like any other ray (2^28 - 100 + 98 < 2^28)
+    check_restated("default", [[big - 100, 0, 0], [0, -(big - 100), 0.5]], [[-1, 0.5, 0], [0, 1, 0]], [64, 64], max_life=64.0)
+    with pytest.raises(ValueError, match="rejected"):
+        cam.line_of_sight([[0.5, 0.5, 0.5], [nan, 0, 0]], [[3.5, 0.5, 0.5], [1, 1, 1]])
+    with pytest.raises(ValueError, match="rejected"):
+        cam.line_of_sight([[0.5, 0.5, 0.5]], [[big, 0.5, 0.5]])
+
+
+# ---- 7. line of sight ------------------------------------------------------------------------------------------------
+def wall_scene():
+    """One chunk of 16^3 at the origin with a solid wall at x = 8."""
+    grid = np.zeros((16, 16, 16), np.uint8)
+    grid[8] = 1
+    one = np.ones((1, 1, 1), np.uint8)
+    return ol.Scene([0, 0, 0], [1, 1, 1], 16, one, one, grid, cr.id_materials(1))
+
+
+def los_rays(a, b):
+    """vel and life of Camera.line_of_sight in numpy: (b - a) / max|b - a| unless that maximum is 0 or 1 (lib.py:310-314)."""
+    d = np.asarray(b, np.float64) - np.asarray(a, np.float64)
+    ref = np.abs(d).max(1)
+    keep = (ref == 0) | (ref == 1)
+    return np.where(keep[:, None], d, d / np.where(keep, 1.0, ref)[:, None]), ref
+
+
+@gpu
+def test_line_of_sight():
+    sc = wall_scene()
+    st = ol.make_settings(width=8, height=6, samples=1, chunk_size=16, dist_max=64)
+    cam = camera_for(sc, settings_store(st), (0.0, 0.0, 0.0), IDENTITY, 1.0)
+    pairs = [((2.5, 5.5, 5.5), (13.5, 6.5, 7.5), False),      # across the wall, either way
+             ((13.5, 6.5, 7.5), (2.5, 5.5, 5.5), False),
+             ((-5.5, 3.5, 3.5), (30.5, 9.5, 3.5), False),     # ... from outside the scene to outside it
+             ((2.5, 5.5, 5.5), (6.5, 12.5, 1.5), True),       # on one side
+             ((10.5, 1.5, 1.5), (14.5, 14.5, 9.5), True),
+             ((2.5, 5.5, 5.5), (7.5, 5.5, 5.5), True),        # the segment ends before the wall
+             ((2.5, 5.5, 5.5), (8.5, 5.5, 5.5), True),        # ... or in it: the voxel at b is a step the life does not cover
+             ((2.5, 5.5, 5.5), (9.5, 5.5, 5.5), False),
+             ((4.5, 4.5, 4.5), (4.5, 4.5, 4.5), True),        # a == b
+             ((8.5, 4.5, 4.5), (8.5, 4.5, 4.5), True),        # ... even inside the wall: no step is taken
+             ((8.5, 4.5, 4.5), (8.5, 9.5, 4.5), False)]       # from inside the wall along it
+    a, b, want = (np.array([p[i] for p in pairs]) for i in range(3))
+    see = cam.line_of_sight(a, b)
+    assert see.dtype == __import__("torch").bool and np.array_equal(see.cpu().numpy(), want)
+    vel, life = los_rays(a, b)
+    assert np.array_equal(cr.march_records(sc, 8, a, vel, life)["material"] == 0, want)
+    # synth64: 300 random pairs agree with cast_rays on the same vel and life, and with the restatement
+    cam, sc = cam_of("synth64")
+    rng = np.random.default_rng(13)
+    a = rng.uniform(-36, 36, (300, 3))
+    b = a + rng.normal(size=(300, 3)) * rng.choice([2.0, 12.0, 30.0], (300, 1))
+    b[:5] = a[:5]
+    b[5:10] = a[5:10] + np.array([1.0, -0.5, 0.25])       # max|b - a| == 1: left as it is
+    vel, life = los_rays(a, b)
+    see = cam.line_of_sight(a, b).cpu().numpy()
+    exp = cr.march_records(sc, 8, a, vel, life)
+    cr.assert_records_equal(cam.cast_rays(a, vel, life, max_life=float(life.max())).numpy(), exp)
+    assert np.array_equal(see, exp["material"] == 0) and 0.1 < see.mean() < 0.9
+
+
+# ---- 8. the hand-out of cast_kernel ----------------------------------------------------------------------------------
+def _handout_child():
+    """1 471 synth64 rays (no multiple of the wave size or of a hand-out chunk); prints the records' digest, the rays marched
+    and the voxels found."""
+    cam, _ = cam_of("synth64")
+    sc, origins, vels, lives, exp = cr.ray_set("synth64")
+    res = cam.cast_rays(origins[:1471], vels[:1471], lives[:1471])
+    rec = res.numpy()
+    assert 1471 % 64 != 0 and (rec["material"] > 0).any()
+    print("HANDOUT", hashlib.sha256(np.ascontiguousarray(rec).tobytes()).hexdigest(), int(res.stats[8]), int(res.stats[4]), int(res.stats[9]))
+
+
+@gpu
+def test_cast_does_not_depend_on_the_hand_out():
+    """cast_kernel under the scheduling knobs the frame kernels are tested with: the records, the rays marched and the voxels
+    found are the same -- and the default setting's are the oracle's."""
+    lines = run_children("import test_gpu_cast as t; t._handout_child()", HANDOUT_KNOBS, "HANDOUT")
+    exp = cr.ray_set("synth64")[4][:1471]
+    want = ["HANDOUT", hashlib.sha256(np.ascontiguousarray(exp).tobytes()).hexdigest(), "1471", str(int((exp["material"] > 0).sum())), "0"]
+    for knobs, words in zip(HANDOUT_KNOBS, lines):
+        assert words == want, (knobs, words, want)
+
+
+# ---- 9. graph capture ------------------------------------------------------------------------------------------------
+@gpu
+def test_cast_is_graph_capturable():
+    import torch
+    cam, _ = cam_of("default")
+    sc, origins, vels, lives, exp = cr.ray_set("default")
+    rec = np.zeros((len(exp), 8))
+    rec[:, 0:3], rec[:, 3:6], rec[:, 6] = origins, vels, lives
+    drec = torch.from_numpy(rec).cuda()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        cam.cast_rays(drec)       # (warm-up on the capturing side: the scene, the allocator)
+    torch.cuda.current_stream().wait_stream(side)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        res = cam.cast_rays(drec)
+    for _ in range(2):
+        res.records.zero_()
+        res._stats_dev.fill_(-1)
+        g.replay()
+        torch.cuda.synchronize()
+        cr.assert_records_equal(res.numpy(), exp)
+        check_stats(res._stats_dev.cpu().numpy(), exp)
+
+
+# ---- 10. fail-loud ---------------------------------------------------------------------------------------------------
+@gpu
+def test_cast_fails_loudly():
+    import torch
+    cam, _ = cam_of("default")
+    sc, origins, vels, lives, exp = cr.ray_set("default")
+    n = 300
+    rec = np.zeros((n, 8))
+    rec[:, 0:3], rec[:, 3:6], rec[:, 6] = origins[:n], vels[:n], lives[:n]
+    drec = torch.from_numpy(rec).cuda()
+    L = nat.lib()
+    st, csc = cam._c_settings(0), cam._c_scene(cam._ensure_scene())
+    hits = torch.full((n * nat.HIT_BYTES,), 0x5a, dtype=torch.uint8, device="cuda")
+    stats = torch.full((nat.NSTATS,), 7, dtype=torch.int64, device="cuda")
+
+    def call(rays, max_life):
+        return L.vrt_cast_rays(C.byref(csc), C.byref(st), rays, n, max_life, hits.data_ptr(), stats.data_ptr(), None)
+
+    assert call(drec.data_ptr(), 0.0) == -1 and call(None, 64.0) == -1
+    torch.cuda.synchronize()
+    assert (stats.cpu().numpy() == 7).all() and (hits.cpu().numpy() == 0x5a).all()     # nothing was launched for them
+    assert call(drec.data_ptr(), 64.0) == 0                                             # ... and the valid call runs
+    torch.cuda.synchronize()
+    cr.assert_records_equal(hits.cpu().numpy().view(HIT_DTYPE), exp[:n])
+    check_stats(stats.cpu().numpy(), exp[:n])
+    with pytest.raises(ValueError, match="max_life"):
+        cam.cast_rays(drec, max_life=-3.0)
+    # the camera still renders
+    h = cam.first_hit(0)
+    assert int(h.stats[8]) == 32 * 24 and (h.numpy()["material"] >= 0).all()
