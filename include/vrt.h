@@ -414,6 +414,53 @@ int vrt_voxelize(const vrt_object* d_objects, int32_t n_objects, const uint8_t* 
                  const int64_t* origin, const int32_t* dims, int32_t chunk_size, const uint32_t* d_chunk_list,
                  int64_t n_list, uint32_t* d_world_table, uint8_t* d_voxels, void* stream);
 
+/* ---- owners of hit records -----------------------------------------------------------------------------
+ * Which OBJECT a hit belongs to, and which voxel of that object's model: what picking, instance images and sprite edits
+ * act on.  vrt_voxelize keeps only the material byte ("the later object wins"); the owner pass asks voxelize's question
+ * again for the hit voxels only -- the objects from LAST to FIRST, the first that has a voxel there owns it -- so it needs
+ * no owner volume, and the two cannot disagree about overlaps, quarter turns or sprite LOD.  One 32-byte record per hit
+ * record. */
+typedef struct vrt_owner {     /* 32 bytes */
+    int32_t object;            /* index into d_objects (merge order); -1: the record is no hit (material <= 0);
+                                  -2: a hit that no object accounts for (orphan) */
+    int32_t resolution;        /* Frame.resolution of the chunk the voxel was read from; 0 when object < 0 */
+    int32_t voxel[3];          /* the world voxel that supplied the material: (cell // r) * r, inside that chunk */
+    int32_t local[3];          /* index into the object's model array [size.x][size.y][size.z], i.e. after the
+                                  quarter-turn addressing -- the voxel a sprite edit would change */
+} vrt_owner;
+/* The words vrt_hit_owners writes into d_stats (every other word 0). */
+enum { VRT_S_OWNER_EXAMINED = 8,   /* records with material > 0 */
+       VRT_S_OWNER_RESOLVED = 4,   /* ... of them resolved to an object */
+       VRT_S_OWNER_ORPHANS = 9,    /* ... of them that no chunk of the scene, or no object, accounts for: the hits came from
+                                      another scene or another object list (examined = resolved + orphans) */
+       VRT_S_OWNER_AMBIGUOUS = 10  /* records that TWO chunks explain; the first was taken (below) */ };
+
+/* d_owners[k] describes d_hits[k] (records of vrt_first_hit, vrt_first_hit_views or vrt_cast_rays; DEVICE arrays of n_hits
+ * records, d_hits 8-byte and d_owners 16-byte aligned).  Every field but `object` of a record with object < 0 is 0.
+ *   scene     the scene the hits were produced against: its camera table with the LOD bytes, its voxels.
+ *   d_objects, n_objects, d_models, d_remap   exactly what the last vrt_voxelize call of that world was given (d_objects
+ *             16-byte aligned).  n_objects = 0 makes every hit an orphan.
+ *   d_stats   [VRT_NSTATS] uint64, zeroed by the callee: the VRT_S_OWNER_* words.
+ * Which voxel a record means.  The march reads the voxel c = (floor(pos) // r) * r of the ray's CURRENT chunk (r: that
+ * chunk's resolution) and finds nothing if c lies outside the chunk.  The record holds floor(pos) and pos, not c, r or the
+ * chunk, and a ray may stand exactly on its chunk's inclusive upper face (init.py:67): floor(pos) is then in the next chunk
+ * while an r that does not divide chunk_size (r = 3) snaps c back into the ray's own.  So the CANDIDATE chunks of a record
+ * are the chunk containing floor(pos) and, for every axis a on which pos[a] is a whole multiple of chunk_size, the chunk
+ * one below on that axis: up to 8, tried in the order (x, y, z lowered) 000, 100, 010, 110, 001, 101, 011, 111 -- the
+ * containing chunk first.  A candidate COUNTS if the table lists it, its c (with its own r) lies inside it and the voxel
+ * byte at c equals the record's material.  The first that counts is taken; if a later one counts too and resolves to
+ * another (object, local), the record is counted in VRT_S_OWNER_AMBIGUOUS: "two chunks explain this record; the first was
+ * taken" -- the result may then name the wrong one of two real voxels of that material, and the count says so.  If none
+ * counts the record is an orphan.
+ * The owner of c is the last object of d_objects with mins <= c < maxs whose model byte at the quarter-turned c - mins is
+ * not 0 (voxelize's loop, backwards); if its remapped material is not the record's, the record is an orphan.
+ * n_hits = 0 only zeroes the statistics; n_hits >= 2^32 is VRT_ERR_ARG; more than 2^28 records are split into launches.
+ * Every argument is checked before any HIP call; nothing is allocated or synchronised, so a call may be captured into a
+ * hipGraph. */
+int vrt_hit_owners(const vrt_scene* scene, const vrt_hit* d_hits, int64_t n_hits,
+                   const vrt_object* d_objects, int32_t n_objects, const uint8_t* d_models, const uint8_t* d_remap,
+                   vrt_owner* d_owners, uint64_t* d_stats, void* stream);
+
 /* Window.chunk_update's selection loop (init.py:447-452) on the device: which world chunks the camera renders this
  * frame and at which LOD.  The voxel blocks stay resident at full resolution; a chunk's LOD is only the resolution
  * byte of its table entry (a Frame of resolution r holds the voxels at coordinates divisible by r, which is what the

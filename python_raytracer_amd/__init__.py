@@ -13,6 +13,7 @@ from .scene import PackedScene
 from .camera import Camera, RenderResult, HitResult, CastResult, release_caches
 from .canvas import Canvas
 from . import world
+from .world import OwnerResult
 
-__all__ = ["Camera", "RenderResult", "HitResult", "CastResult", "release_caches", "Canvas", "world", "Material", "Frame", "PackedScene", "data", "lib", "vec3", "quaternion", "rgb",
+__all__ = ["Camera", "RenderResult", "HitResult", "CastResult", "release_caches", "Canvas", "world", "OwnerResult", "Material", "Frame", "PackedScene", "data", "lib", "vec3", "quaternion", "rgb",
            "store", "material", "material_background", "make_settings", "load_settings", "pixel_partition"]

@@ -36,6 +36,8 @@ COUNTER_NAMES = ["lookup", "nbr", "resnap", "chunk_get", "hit", "draw", "adv", "
 S_RAYS, S_RNG_RETRACED, S_RNG_EXHAUSTED, S_TRAV_OUTSIDE, S_POOL_GROUPS, S_STALLED, S_LOOKAHEAD_GROUPS = 8, 9, 10, 11, 12, 13, 14
 S_RAYGEN_GROUPS = 15
 S_CAST_REJECTED = 9   # vrt_cast_rays only: rays the device refused (VRT_S_CAST_REJECTED)
+# vrt_hit_owners only (VRT_S_OWNER_*): records examined, resolved to an object, orphans, explained by two chunks
+S_OWNER_EXAMINED, S_OWNER_RESOLVED, S_OWNER_ORPHANS, S_OWNER_AMBIGUOUS = 8, 4, 9, 10
 
 
 def needs_build():
@@ -109,6 +111,17 @@ class VrtCastRay(C.Structure):
 
 CAST_RAY_BYTES = 64
 HIT_REJECTED = -2   # vrt_hit.material of a ray vrt_cast_rays refused
+
+
+
+class VrtOwner(C.Structure):
+    """vrt_owner (include/vrt.h): which object and which voxel of its model a hit record belongs to, 32 bytes."""
+    _fields_ = [("object", C.c_int32), ("resolution", C.c_int32), ("voxel", C.c_int32 * 3), ("local", C.c_int32 * 3)]
+
+
+OWNER_FIELDS = [("object", "<i4"), ("resolution", "<i4"), ("voxel", "<i4", 3), ("local", "<i4", 3)]
+OWNER_BYTES = 32
+OWNER_NONE, OWNER_ORPHAN = -1, -2   # vrt_owner.object of a record that is no hit / that no object accounts for
 
 _lib = None
 
@@ -192,6 +205,8 @@ def lib():
                                     C.POINTER(VrtTraversed), vp, vp]
     L.vrt_voxelize.restype = C.c_int
     L.vrt_voxelize.argtypes = [vp, i32, vp, vp, C.POINTER(i64), C.POINTER(i32), i32, vp, i64, vp, vp, vp]
+    L.vrt_hit_owners.restype = C.c_int
+    L.vrt_hit_owners.argtypes = [C.POINTER(VrtScene), vp, i64, vp, i32, vp, vp, vp, vp, vp]
     L.vrt_canvas_blit.restype = C.c_int
     L.vrt_canvas_blit.argtypes = [vp, vp, i32, i32, vp, i64, vp]
     L.vrt_profile_begin.restype = C.c_int
@@ -218,7 +233,8 @@ EXPORTS = ["vrt_abi_version", "vrt_status_string", "vrt_last_hip_error", "vrt_de
            "vrt_draw_table_bytes", "vrt_draw_table_build", "vrt_ray_table_bytes", "vrt_ray_table_build",
            "vrt_pow_memo_create", "vrt_occupancy_build", "vrt_canvas_blit", "vrt_world_tables_bytes", "vrt_world_tables_build",
            "vrt_trace_workspace_bytes", "vrt_trace_rays", "vrt_rng_draws",
-           "vrt_synth_volume", "vrt_profile_begin", "vrt_profile_begin_kinds", "vrt_profile_end", "vrt_select_chunks", "vrt_voxelize"]
+           "vrt_synth_volume", "vrt_profile_begin", "vrt_profile_begin_kinds", "vrt_profile_end", "vrt_select_chunks", "vrt_voxelize",
+           "vrt_hit_owners"]
 
 
 PLAN_FIELDS = ("launches", "pool", "wt_on", "trav_words", "bm_window", "ct_cells", "n_materials", "dyn_bytes", "static_bytes")

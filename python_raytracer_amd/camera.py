@@ -1094,6 +1094,22 @@ class Camera:
                                  "|a| + (max|b - a| + 2 * chunk_size + 2) < 2**28)" % (int(bad.sum()), int(bad.numel())))
         return res.material == 0
 
+    def pick(self, x, y, world):
+        """The voxel under the cursor: what pixel (x, y) sees, as something to act on.  Runs first_hit() on that one pixel
+        (its first sample) and world.owners() on the record; `world` is the DeviceWorld whose scene this camera renders.
+        Returns None where the pixel sees nothing, else (Object, local, voxel, depth): the Object instance of world.order,
+        the index (x, y, z) into its sprite's model array -- the voxel a sprite edit would change --, the world voxel, and
+        the ray's step at the hit.  Copies the two records to the host, so it SYNCHRONISES; for many pixels use first_hit()
+        and owners() themselves.  Raises RuntimeError if no object of `world` accounts for the hit (another world's)."""
+        hit = self.first_hit(pixels=[[int(x), int(y)]])
+        own = world.owners(hit, self).numpy()[0]
+        if int(own["object"]) == nat.OWNER_NONE:
+            return None
+        if int(own["object"]) < 0:
+            raise RuntimeError("pick(%d, %d): no object of this world accounts for the voxel the pixel sees" % (x, y))
+        return (world.order[int(own["object"])], tuple(int(v) for v in own["local"]), tuple(int(v) for v in own["voxel"]),
+                float(hit.numpy()["step"][0]))
+
     def tile(self, thread, t=0):
         """Reference signature and return triple (init.py:126-150): RGBA8 bytes of the full window (pixels of other
         threads transparent), the traversed chunk list, and the thread index."""

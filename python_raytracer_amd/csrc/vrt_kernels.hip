@@ -3775,6 +3775,170 @@ __global__ void __launch_bounds__(VRT_BLOCK) voxelize_kernel(const vrt_object* o
 }
 
 // ---------------------------------------------------------------------------------------------
+// owner pass (vrt_hit_owners): which object, and which voxel of its model, a hit record belongs to
+// ---------------------------------------------------------------------------------------------
+struct OwnerParams {
+    const vrt_hit* hits;
+    vrt_owner* owners;
+    int64_t n;
+    const vrt_object* objects;
+    const uint8_t* models;
+    const uint8_t* remap;
+    const uint32_t* table;
+    const uint8_t* voxels;
+    unsigned long long* stats;
+    int32_t n_objects, n_slots, cs, cs_shift;
+    int32_t origin[3], dims[3];
+};
+#define VRT_OWNER_TILE 128   // objects staged in LDS at a time by owner_kernel<true>: 8 KiB
+struct OwnerFound {
+    int object, lx, ly, lz;
+};
+
+// voxelize_kernel's question for one object: the model byte object `o` holds at world voxel (wx, wy, wz), 0 = none
+__device__ __forceinline__ int owner_probe(const vrt_object& o, const uint8_t* models, int wx, int wy, int wz, int& x, int& y, int& z) {
+    if (wx < o.mins[0] || wy < o.mins[1] || wz < o.mins[2] || wx >= o.maxs[0] || wy >= o.maxs[1] || wz >= o.maxs[2]) return 0;
+    x = wx - o.mins[0], y = wy - o.mins[1], z = wz - o.mins[2];
+    rotate_index(o, x, y, z);
+    if (x < 0 || y < 0 || z < 0 || x >= o.size[0] || y >= o.size[1] || z >= o.size[2]) return 0;
+    return models[o.model + ((int64_t)x * o.size[1] + y) * o.size[2] + z];
+}
+
+// the objects from last to first, read from memory (the index is the same in every lane: uniform loads); the first that has a
+// voxel at (wx, wy, wz) owns it -- voxelize_kernel's "the later object wins", asked from the other end.  -2: no object accounts
+// for `material` there.  Stops when no lane of the wave is searching any more.
+__device__ __forceinline__ OwnerFound owner_search(const OwnerParams& P, bool searching, int wx, int wy, int wz, int material) {
+    OwnerFound f = {-2, 0, 0, 0};
+    for (int k = P.n_objects - 1; k >= 0 && __ballot(searching) != 0ull; k--) {
+        const vrt_object& o = P.objects[k];
+        if (!searching) continue;
+        int x, y, z;
+        const int local = owner_probe(o, P.models, wx, wy, wz, x, y, z);
+        if (local) {
+            if (P.remap[o.remap + local] == material) f = OwnerFound{k, x, y, z};
+            searching = false;
+        }
+    }
+    return f;
+}
+
+// (c // r) * r for one coordinate, Python's floor division
+__device__ __forceinline__ int owner_snap(int f, int r) {
+    if (r == 1) return f;
+    if (r == 2) return f & ~1;
+    int q = f / r;
+    if (f - q * r < 0) q--;
+    return q * r;
+}
+
+// Candidate chunk `m` of a record (bit a of m: the chunk one below the containing one on axis a): if the camera table lists
+// it, the voxel (cell // r) * r lies inside it and holds `material`, returns its resolution and the voxel; else 0.
+__device__ __forceinline__ int owner_candidate(const OwnerParams& P, int m, int fx, int fy, int fz, int material, int& cx, int& cy, int& cz) {
+    const int kx = ((fx - P.origin[0]) >> P.cs_shift) - (m & 1), ky = ((fy - P.origin[1]) >> P.cs_shift) - ((m >> 1) & 1),
+              kz = ((fz - P.origin[2]) >> P.cs_shift) - ((m >> 2) & 1);
+    if ((unsigned)kx >= (unsigned)P.dims[0] || (unsigned)ky >= (unsigned)P.dims[1] || (unsigned)kz >= (unsigned)P.dims[2]) return 0;
+    const uint32_t entry = P.table[((int64_t)kx * P.dims[1] + ky) * P.dims[2] + kz];
+    const int slot = (int)(entry & 0xffffffu) - 1, r = (int)(entry >> 24);
+    if (slot < 0 || slot >= P.n_slots || r < 1) return 0;
+    cx = owner_snap(fx, r), cy = owner_snap(fy, r), cz = owner_snap(fz, r);
+    const int lx = cx - (P.origin[0] + (kx << P.cs_shift)), ly = cy - (P.origin[1] + (ky << P.cs_shift)),
+              lz = cz - (P.origin[2] + (kz << P.cs_shift));
+    if ((unsigned)lx >= (unsigned)P.cs || (unsigned)ly >= (unsigned)P.cs || (unsigned)lz >= (unsigned)P.cs) return 0;
+    const int byte = P.voxels[((int64_t)slot << (3 * P.cs_shift)) + voxel_offset(P.cs, lx, ly, lz)];
+    return byte == material ? r : 0;
+}
+
+// One lane per record.  Every wave reads the object records from memory with uniform loads and stops on its own -- the
+// shipped form; LDS_TILES: they are staged in LDS, VRT_OWNER_TILE at a time, by the whole workgroup, which then walks the list
+// in step (the measured alternative: equal at 8 and 256 objects, 10 % slower at 4096, profiles/owners_bench.json).
+template <bool LDS_TILES>
+__global__ void __launch_bounds__(VRT_BLOCK) owner_kernel(OwnerParams P) {
+    __shared__ __attribute__((aligned(16))) vrt_object s_obj[LDS_TILES ? VRT_OWNER_TILE : 1];
+    const int64_t i = (int64_t)blockIdx.x * VRT_BLOCK + threadIdx.x;
+    const bool live = i < P.n;
+    int material = 0, fx = 0, fy = 0, fz = 0;
+    unsigned low = 0;  // bit a: pos[a] is a whole multiple of chunk_size, so the ray may still have stood in the chunk below
+    if (live) {
+        const vrt_hit& h = P.hits[i];
+        material = h.material;
+        if (material > 0) {
+            fx = h.cell[0], fy = h.cell[1], fz = h.cell[2];
+            const int cm = P.cs - 1;
+            low = (unsigned)(h.pos[0] == (double)fx && (fx & cm) == 0) | (unsigned)(h.pos[1] == (double)fy && (fy & cm) == 0) << 1 |
+                  (unsigned)(h.pos[2] == (double)fz && (fz & cm) == 0) << 2;
+        }
+    }
+    const bool examined = material > 0;
+    // the first candidate that counts, in the order 0 (the containing chunk), x, y, xy, z, xz, yz, xyz; `later`: the others that count
+    int res = 0, cx = 0, cy = 0, cz = 0;
+    unsigned later = 0;
+    if (examined) {
+        for (int m = 0; m < 8; m++) {
+            if (m & ~low) continue;
+            int tx, ty, tz;
+            const int r = owner_candidate(P, m, fx, fy, fz, material, tx, ty, tz);
+            if (!r) continue;
+            if (!res) res = r, cx = tx, cy = ty, cz = tz;
+            else later |= 1u << m;
+        }
+    }
+    bool searching = res != 0;
+    OwnerFound f = {-2, 0, 0, 0};
+    if (LDS_TILES) {
+        for (int hi = P.n_objects; hi > 0; hi -= VRT_OWNER_TILE) {
+            if (!__syncthreads_or(searching)) break;  // (also: every lane has finished reading the previous tile)
+            const int lo = hi > VRT_OWNER_TILE ? hi - VRT_OWNER_TILE : 0;
+            // 64-byte records as four 16-byte words each: two words per thread
+            const int4* src = reinterpret_cast<const int4*>(P.objects + lo);
+            int4* dst = reinterpret_cast<int4*>(s_obj);
+            for (int w = threadIdx.x; w < (hi - lo) * 4; w += VRT_BLOCK) dst[w] = src[w];
+            __syncthreads();
+            for (int k = hi - lo - 1; k >= 0 && __ballot(searching) != 0ull; k--) {
+                if (!searching) continue;
+                const vrt_object& o = s_obj[k];
+                int x, y, z;
+                const int local = owner_probe(o, P.models, cx, cy, cz, x, y, z);
+                if (local) {
+                    if (P.remap[o.remap + local] == material) f = OwnerFound{lo + k, x, y, z};
+                    searching = false;
+                }
+            }
+        }
+    } else {
+        f = owner_search(P, searching, cx, cy, cz, material);
+    }
+    // two chunks explain this record (rare): the first was taken, and the record is counted if another resolves differently
+    bool ambiguous = false;
+    if (later) {
+        for (int m = 1; m < 8; m++) {
+            if (!((later >> m) & 1u)) continue;
+            int tx, ty, tz;
+            owner_candidate(P, m, fx, fy, fz, material, tx, ty, tz);
+            const OwnerFound g = owner_search(P, true, tx, ty, tz, material);
+            ambiguous |= g.object != f.object || g.lx != f.lx || g.ly != f.ly || g.lz != f.lz;
+        }
+    }
+    if (live) {
+        int4 a = {-1, 0, 0, 0}, b = {0, 0, 0, 0};
+        if (examined) {
+            a.x = f.object;
+            if (f.object >= 0) a = int4{f.object, res, cx, cy}, b = int4{cz, f.lx, f.ly, f.lz};
+        }
+        int4* out = reinterpret_cast<int4*>(P.owners + i);
+        out[0] = a;
+        out[1] = b;
+    }
+    const unsigned n_exam = (unsigned)__popcll(__ballot(examined)), n_own = (unsigned)__popcll(__ballot(examined && f.object >= 0)),
+                   n_amb = (unsigned)__popcll(__ballot(ambiguous));
+    if ((threadIdx.x & 63) == 0) {
+        if (n_exam) atomicAdd(&P.stats[VRT_S_OWNER_EXAMINED], (unsigned long long)n_exam);
+        if (n_own) atomicAdd(&P.stats[VRT_S_OWNER_RESOLVED], (unsigned long long)n_own);
+        if (n_exam - n_own) atomicAdd(&P.stats[VRT_S_OWNER_ORPHANS], (unsigned long long)(n_exam - n_own));
+        if (n_amb) atomicAdd(&P.stats[VRT_S_OWNER_AMBIGUOUS], (unsigned long long)n_amb);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // camera chunk selection: Window.chunk_update's loop over chunks (init.py:447-452)
 // ---------------------------------------------------------------------------------------------
 struct SelectParams {
@@ -5609,6 +5773,54 @@ int vrt_voxelize(const vrt_object* d_objects, int32_t n_objects, const uint8_t* 
     hipLaunchKernelGGL(voxelize_kernel, dim3((unsigned)blocks), dim3(VRT_BLOCK), 0, stream, d_objects, (int)n_objects, d_models,
                        d_remap, (int)origin[0], (int)origin[1], (int)origin[2], (int)dims[1], (int)dims[2], (int)cs,
                        d_chunk_list, d_world_table, d_voxels);
+    HIP_TRY(hipGetLastError());
+    return VRT_OK;
+}
+
+int vrt_hit_owners(const vrt_scene* sc, const vrt_hit* d_hits, int64_t n_hits, const vrt_object* d_objects, int32_t n_objects,
+                   const uint8_t* d_models, const uint8_t* d_remap, vrt_owner* d_owners, uint64_t* d_stats, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    // (every check comes before any HIP call)
+    if (!sc || !d_stats || n_hits < 0 || n_hits >= (1ll << 32) || n_objects < 0) return VRT_ERR_ARG;
+    if (n_hits > 0 && (!d_hits || !d_owners || ((uintptr_t)d_hits & 7) != 0 || ((uintptr_t)d_owners & 15) != 0)) return VRT_ERR_ARG;
+    if (n_objects > 0 && (!d_objects || !d_models || !d_remap || ((uintptr_t)d_objects & 15) != 0)) return VRT_ERR_ARG;
+    const int cs = sc->chunk_size;
+    if (cs < 8 || cs > 256 || (cs & (cs - 1))) return VRT_ERR_ARG;
+    if (!sc->d_chunk_table || sc->n_slots < 0 || sc->n_slots >= (1 << 24) || (sc->n_slots > 0 && !sc->d_voxels)) return VRT_ERR_ARG;
+    OwnerParams P;
+    int64_t cells = 1;
+    for (int a = 0; a < 3; a++) {
+        if (sc->dims[a] <= 0 || (sc->origin[a] % cs) != 0) return VRT_ERR_ARG;
+        if (sc->origin[a] < -(1ll << 28) || sc->origin[a] + (int64_t)sc->dims[a] * cs > (1ll << 28)) return VRT_ERR_ARG;
+        P.origin[a] = (int32_t)sc->origin[a];
+        P.dims[a] = sc->dims[a];
+        cells *= sc->dims[a];
+    }
+    if (cells >= (1ll << 31)) return VRT_ERR_ARG;
+    int shift = 0;
+    while ((1 << shift) < cs) shift++;
+    P.cs = cs;
+    P.cs_shift = shift;
+    P.n_slots = sc->n_slots;
+    P.table = sc->d_chunk_table;
+    P.voxels = sc->d_voxels;
+    P.objects = d_objects;
+    P.n_objects = n_objects;
+    P.models = d_models;
+    P.remap = d_remap;
+    P.stats = (unsigned long long*)d_stats;
+    frame_begin(d_stats, nullptr, 0, nullptr, 0, nullptr, stream);
+    // object records by uniform loads from memory: the measured choice (profiles/owners_bench.json).  VRT_OWNER_LDS=1 stages
+    // them in LDS tiles instead -- the alternative of that measurement, kept parity-tested (read at every call: the tests run both)
+    const bool lds = env_int("VRT_OWNER_LDS", 0) != 0;
+    const int64_t per_launch = batch_rays();
+    for (int64_t r0 = 0; r0 < n_hits; r0 += per_launch) {
+        P.n = n_hits - r0 < per_launch ? n_hits - r0 : per_launch;
+        P.hits = d_hits + r0;
+        P.owners = d_owners + r0;
+        if (lds) hipLaunchKernelGGL(owner_kernel<true>, dim3((unsigned)grid_for(P.n)), dim3(VRT_BLOCK), 0, stream, P);
+        else hipLaunchKernelGGL(owner_kernel<false>, dim3((unsigned)grid_for(P.n)), dim3(VRT_BLOCK), 0, stream, P);
+    }
     HIP_TRY(hipGetLastError());
     return VRT_OK;
 }
