@@ -1649,6 +1649,15 @@ __device__ __forceinline__ bool take_ray_views(const MarchParams& P, const March
 #ifndef VRT_PASS_COUNTS
 #define VRT_PASS_COUNTS 0
 #endif
+// march_pool_kernel: passes that march the rays they have just fed instead of ending (a build-time switch, so that no
+// pass carries a branch it never takes).  Bit 0: an ENDED pass enters the march loop after its refill once P.pool_keep
+// lanes march; bit 1: the HIT body runs in front of the march loop and a HIT pass enters the loop under the same rule
+// (tail mode then runs HIT before its one step).  Scheduling only, never a result.  Measured in profiles/pool_passes_ab.md:
+// both legs config 3 5.03 against 5.26 ms, the HIT leg alone 5.17, the ENDED leg alone 5.37 (128 VGPRs, 11 spilled SGPRs: with
+// the HIT body behind the loop the compiler finds no room) -- 3 ships, 0 gives the device code from before the switch
+#ifndef VRT_POOL_FUSE
+#define VRT_POOL_FUSE 3
+#endif
 // the march step's view of the kernel arguments: held in scalar registers (the step runs every pass and needs them at
 // once), or re-read like the slow bodies do (march_step_w's one-at-a-time path; -DVRT_FRESH_MARCH=1)
 template <bool FRESH>
@@ -3235,7 +3244,8 @@ __global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) cast_kernel(Mar
 // ---- march_pool_kernel: the same bodies, rays regrouped between the lanes of a wave through LDS ------------------------
 // march_kernel executes a body for the lanes that wait for it while the others idle: per VALU instruction 49 % of the
 // lanes are active at config 3 (profiles/r02_v7_sq_c3_summary.txt), and the kernel is bound by VALU issue.  Here every
-// wave owns VRT_POOL_SLOTS parked rays in LDS besides the 64 in its lanes.  A pass picks ONE body -- HIT once t_hit rays
+// wave owns VRT_POOL_SLOTS parked rays in LDS besides the 64 in its lanes.  A pass picks ONE body (an ENDED or HIT
+// pass may go on to march the rays it has fed: VRT_POOL_FUSE) -- HIT once t_hit rays
 // wait for it anywhere in the wave's pool, ENDED (+ refill) once t_end do, else MARCH -- and first brings rays of that
 // state into the lanes that hold something else: such a lane exchanges its whole ray (18 eight-byte words and its state)
 // with a parked one by ds_wrxchg, or, when the pool has room and the launch has rays left, parks its waiting ray in a free
@@ -3445,6 +3455,7 @@ __global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) march_pool_kern
     int32_t tot[C_NLOCAL];
 #pragma unroll
     for (int j = 0; j < C_NLOCAL; j++) tot[j] = 0;
+    constexpr bool FUSE_ENDED = (VRT_POOL_FUSE & 1) != 0, FUSE_HIT = (VRT_POOL_FUSE & 2) != 0;  // (see VRT_POOL_FUSE)
     unsigned pass = 0;
     int stalled = 0;  // MARCH passes that found nothing to march
     for (;; pass++) {
@@ -3581,13 +3592,32 @@ __global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) march_pool_kern
         unsigned long long dg_t3 = DG_TIME();
         DG_ADD(DG_CYC_REFILL, dg_t3 - dg_t2);
 #endif
+        // ------------------------------------------------------------------ HIT, in front of the march when HIT passes feed it
+#ifdef VRT_DIAG
+        unsigned long long dg_t3h = dg_t3;  // (where the march's cycle bracket opens: behind the HIT body if it runs here)
+#endif
+        if constexpr (FUSE_HIT) {
+#ifdef VRT_DIAG
+            if ((target == LANE_HIT || tail) && __ballot(state == LANE_HIT)) { DG_ADD(DG_HIT_EXEC, 1); DG_ADD(DG_HIT_LANES, __popcll(__ballot(state == LANE_HIT))); }
+#endif
+            VRT_MARK("hit");
+            if ((tv & 4) && state == LANE_HIT) hit_body<RESMODE, false>(P, C, r, state, tot, dg);
+#ifdef VRT_DIAG
+            dg_t3h = DG_TIME();
+            DG_ADD(DG_CYC_HIT, dg_t3h - dg_t3);
+#endif
+        }
         VRT_MARK("march");
         // ------------------------------------------------------------------ MARCH steps: further ones at once while most lanes
-        // still march (a pass costs ~40 instructions before its body starts)
-        for (int it = 0; target == LANE_MARCH && it < (tail ? 1 : P.max_iters); it++) {
+        // still march (the head of a pass -- slot states, ballots, target choice, the exchange's set-up -- is ~140 scalar and
+        // 70-105 VALU instructions before its body starts).  A pass that fed the march (VRT_POOL_FUSE: the
+        // ENDED pass's refill, the HIT body's survivors) takes its first step under the rule for a further one, P.pool_keep
+        // lanes; it is no MARCH pass, so finding nothing to march is not a stall
+        const bool fed = (FUSE_ENDED && target == LANE_ENDED) || (FUSE_HIT && target == LANE_HIT);  // (wave-uniform; never in tail mode)
+        for (int it = 0; (target == LANE_MARCH || fed) && it < (tail ? 1 : P.max_iters); it++) {
             const int marching = (int)__popcll(__ballot(state == LANE_MARCH));
-            stalled += (it == 0 && marching == 0 && !tail) ? 1 : 0;  // (a MARCH pass with nothing to march: see the top of the loop)
-            if (marching == 0 || (it > 0 && marching < P.pool_keep)) break;
+            stalled += (it == 0 && marching == 0 && !tail && !fed) ? 1 : 0;  // (a MARCH pass with nothing to march: see the top of the loop)
+            if (marching == 0 || ((it > 0 || fed) && marching < P.pool_keep)) break;
 #ifdef VRT_DIAG
             DG_ADD(DG_ITERS, 1);
             DG_ADD(DG_MARCH_LANES, marching);
@@ -3599,17 +3629,21 @@ __global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) march_pool_kern
         }
 #ifdef VRT_DIAG
         unsigned long long dg_t4 = DG_TIME();
-        DG_ADD(DG_CYC_MARCH, dg_t4 - dg_t3);
-        if ((target == LANE_HIT || tail) && __ballot(state == LANE_HIT)) { DG_ADD(DG_HIT_EXEC, 1); DG_ADD(DG_HIT_LANES, __popcll(__ballot(state == LANE_HIT))); }
+        DG_ADD(DG_CYC_MARCH, dg_t4 - dg_t3h);
 #endif
-        VRT_MARK("hit");
         // ------------------------------------------------------------------ HIT
-        if ((tv & 4) && state == LANE_HIT) hit_body<RESMODE, false>(P, C, r, state, tot, dg);
+        if constexpr (!FUSE_HIT) {
+#ifdef VRT_DIAG
+            if ((target == LANE_HIT || tail) && __ballot(state == LANE_HIT)) { DG_ADD(DG_HIT_EXEC, 1); DG_ADD(DG_HIT_LANES, __popcll(__ballot(state == LANE_HIT))); }
+#endif
+            VRT_MARK("hit");
+            if ((tv & 4) && state == LANE_HIT) hit_body<RESMODE, false>(P, C, r, state, tot, dg);
+        }
         VRT_MARK("pass_end");
         // the events this lane counted in this pass (HIT passes: the shader's; MARCH passes: lookups and advances)
         if (PASS_COUNTS) {
             lds_u32* col = C.tot + (lane & (VRT_TOT_COLS - 1));
-            const bool ran_march = tail || target == LANE_MARCH, ran_hit = tail || target == LANE_HIT;  // (wave-uniform)
+            const bool ran_march = tail || target == LANE_MARCH || fed, ran_hit = tail || target == LANE_HIT;  // (wave-uniform)
             if (ran_hit) {
                 __hip_atomic_fetch_add(col + VRT_C_NBR * VRT_TOT_COLS, (uint32_t)tot[C_NBR], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 __hip_atomic_fetch_add(col + VRT_C_CHUNK_GET * VRT_TOT_COLS, (uint32_t)tot[C_CGET], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);

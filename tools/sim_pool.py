@@ -5,6 +5,7 @@ with the rates of tools/diag_march.py; a workgroup's waves advance in parallel, 
 body it executes whatever the number of active lanes.
 
     python tools/sim_pool.py [c3|c5]
+    python tools/sim_pool.py passes [c3|c5]     march_pool_kernel's shipped pass policy and its fused passes (VRT_POOL_FUSE)
 """
 import random
 import sys
@@ -253,7 +254,122 @@ def private_pool(c, rng, parked=48, n_rays=200000, t_hit=56, t_end=56, swap_min=
     return cost / done, out
 
 
+def shipped_pool(c, rng, fuse=0, slots=48, n_rays=200000, t_hit=40, t_end=60, swap_min=8, refill_min=8, keep=40, max_iters=3):
+    """march_pool_kernel's pass loop as shipped (python_raytracer_amd/csrc/vrt_kernels.hip): one target per pass -- HIT once
+    t_hit rays wait anywhere in the wave's 64 lanes + `slots` parked places, ENDED (+ refill) once t_end do, else MARCH --,
+    the exchange that brings rays of the target's state into the lanes (or parks waiting rays in free slots for fresh ones),
+    then the bodies in source order.  fuse: -DVRT_POOL_FUSE's bits -- 1: an ENDED pass enters the march loop after its refill
+    once `keep` lanes march; 2: the HIT body runs before the march loop and a HIT pass enters it under the same rule.
+    Without rays left to hand out every pass runs all three bodies (tail mode).  Counts, not costs: passes, executions of each
+    body and the lanes they find."""
+    lanes = [None] * 64      # a lane's state, or None
+    park = []                # states of the parked rays
+    done = issued = passes = 0
+    execs = {"march": 0, "hit": 0, "end": 0, "refill": 0, "xchg": 0}
+    lane_sum = {"march": 0, "hit": 0, "end": 0, "refill": 0, "xchg": 0}
+
+    def hit_body(st):
+        return E if rng.random() < c["p_break"] else M
+
+    def march_body(st):
+        u = rng.random()
+        return H if u < c["p_hit"] else (E if u < c["p_hit"] + c["p_end"] else M)
+
+    def run(name, state, body):
+        n = 0
+        for i in range(64):
+            if lanes[i] == state:
+                lanes[i] = body(state)
+                n += 1
+        if n:
+            execs[name] += 1
+            lane_sum[name] += n
+        return n
+
+    while True:
+        passes += 1
+        n = {st: lanes.count(st) + park.count(st) for st in (M, H, E)}
+        idle = lanes.count(None)
+        rays_left = issued < n_rays
+        can_add = rays_left and (idle > 0 or len(park) < slots)
+        if rays_left:
+            if n[H] >= t_hit:
+                target = H
+            elif n[E] >= t_end:
+                target = E
+            elif n[M] > 0 or can_add:
+                target = M
+            else:
+                target = H if n[H] >= n[E] else E
+        else:
+            if n[M] + n[H] + n[E] == 0:
+                break
+            target = M
+        tail = not rays_left
+        # the exchange: lanes that hold another state first, then idle lanes, take the parked rays of the target's state; under
+        # MARCH the ray holders left over park their rays in free slots and go idle (for a fresh ray)
+        wanted = (lambda st: st is not None) if tail else (lambda st: st == target)
+        others = [i for i in range(64) if lanes[i] is not None and not wanted(lanes[i])] + [i for i in range(64) if lanes[i] is None]
+        n_a = 64 - idle - sum(1 for st in lanes if st is not None and wanted(st))
+        src = [k for k, st in enumerate(park) if wanted(st)]
+        take = min(len(others), len(src))
+        free = slots - len(park)
+        evict = min(max(n_a - len(src), 0), free) if (target == M and rays_left and not tail) else 0
+        in_lanes = sum(1 for st in lanes if st is not None and wanted(st))
+        if take + evict >= (1 if tail else swap_min) or (take + evict > 0 and in_lanes == 0):
+            execs["xchg"] += 1
+            lane_sum["xchg"] += take + evict
+            for i, k in zip(others[:take], src[:take]):
+                lanes[i], park[k] = park[k], lanes[i]
+            park[:] = [st for st in park if st is not None]
+            for i in others[take:take + evict]:
+                park.append(lanes[i])
+                lanes[i] = None
+        if tail or target == E:
+            k = run("end", E, lambda st: None)
+            done += k
+        if target != H and issued < n_rays:
+            idle_now = [i for i in range(64) if lanes[i] is None]
+            if idle_now and (target == E or len(idle_now) >= refill_min or lanes.count(M) == 0):
+                take_n = min(len(idle_now), n_rays - issued)
+                for i in idle_now[:take_n]:
+                    lanes[i] = M
+                issued += take_n
+                execs["refill"] += 1
+                lane_sum["refill"] += take_n
+        if (fuse & 2) and (tail or target == H):
+            run("hit", H, hit_body)
+        fed = ((fuse & 1) and target == E) or ((fuse & 2) and target == H)
+        if target == M or fed:
+            for it in range(1 if tail else max_iters):
+                m = lanes.count(M)
+                if m == 0 or ((it > 0 or fed) and m < keep):
+                    break
+                run("march", M, march_body)
+        if not (fuse & 2) and (tail or target == H):
+            run("hit", H, hit_body)
+    out = {k: round(lane_sum[k] / max(1, execs[k]), 1) for k in lane_sum}
+    return passes * 64 / done, {k: execs[k] * 64 / done for k in execs}, out
+
+
+def passes_table(name):
+    c = CFG[name]
+    pol = dict(c3=(40, 60, 8, 8, 40, 3), c5=(48, 32, 4, 8, 40, 5))[name]   # pool_policy's defaults
+    base = None
+    print("%s, shipped knobs %s, 48 slots; per ray x 64" % (name, " / ".join(str(v) for v in pol)))
+    for fuse, label in ((0, "shipped"), (1, "ENDED + refill falls into the march"), (2, "HIT falls into the march"), (3, "both")):
+        p, ex, ln = shipped_pool(c, random.Random(1), fuse=fuse, t_hit=pol[0], t_end=pol[1], swap_min=pol[2], refill_min=pol[3],
+                                 keep=pol[4], max_iters=pol[5])
+        base = base or (p, ex["march"])
+        print("fuse %d  %-36s passes %5.2f (%+5.1f%%)  march steps %5.2f (%+5.1f%%) at %4.1f lanes  hit %4.2f at %4.1f  ended %4.2f at %4.1f  exchanges %4.2f" % (
+            fuse, label, p, 100 * (p / base[0] - 1), ex["march"], 100 * (ex["march"] / base[1] - 1), ln["march"], ex["hit"], ln["hit"],
+            ex["end"], ln["end"], ex["xchg"]))
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "passes":
+        passes_table(sys.argv[2] if len(sys.argv) > 2 else "c3")
+        sys.exit(0)
     name = sys.argv[1] if len(sys.argv) > 1 else "c3"
     c = CFG[name]
     rng = random.Random(1)
