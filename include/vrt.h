@@ -132,8 +132,9 @@ typedef struct vrt_ray {
 } vrt_ray;
 
 /* Frame statistics written by vrt_render_tile into d_stats (16 x uint64, zeroed by the callee):
- *   [0..7] event counters summed over rays (VRT_C_*), [8] primary rays traced, [9] rays that needed more
- *   random draws than the fast table held and were re-traced, [10] rays whose draws exceeded every table
+ *   [0..7] event counters summed over rays (VRT_C_*), [8] primary rays traced to their end, [9] those of them that needed
+ *   more random draws than the fast table held and were re-traced (a ray counted in [10] is in neither), [10] rays whose
+ *   draws exceeded every table or that found a re-trace list full -- vrt_workspace_bytes has the capacities --
  *   (result invalid -> the Python wrapper raises), [11] chunk visits outside the traversed box, [12] workgroups of the
  *   frame's march that ran march_pool_kernel (rays regrouped between lanes through LDS; 0: march_kernel, one ray per lane
  *   -- which one runs is the library's choice by launch size and LDS room, and never changes a result).  Bits 32 and up of
@@ -204,7 +205,10 @@ int vrt_plan_build(const vrt_settings* st, const int32_t* d_pixels_xy, int64_t n
  * fast_draws: random draws kept per distinct seed in the frame's table, 32 or 64; rays that consume more are re-traced
  * with a private 113-draw row (and the few that outrun that, with a 1024-draw row from a full-state MT19937), so the
  * choice changes speed only, never results (32 suits max_bounces <= ~4; scenes where many rays take > 9 rough hits
- * want 64). */
+ * want 64) -- as long as the re-trace lists hold the rays: per march launch (at most 2^28 ray slots) the first re-trace list
+ * holds 1/64 of the launch's ray slots, held between 2^18 and 2^22 (the whole launch if it has fewer than 2^18), and the
+ * second 4096 rays.  A ray that finds its list full, or that outruns the 1024-draw row, is not completed: its outputs are
+ * undefined and it is counted in d_stats[VRT_S_RNG_EXHAUSTED] instead of d_stats[VRT_S_RAYS]. */
 enum { VRT_WS_DRAW_TABLE = 1, VRT_WS_RAY_TABLE = 2 };
 int vrt_workspace_bytes(const vrt_settings* st, int64_t n_px, int64_t n_distinct, int32_t fast_draws, int32_t external,
                         int64_t* bytes);

@@ -20,6 +20,13 @@ def _xyz(v):
     return [float(v.x), float(v.y), float(v.z)]
 
 
+# why a frame's or a batch's rays are left over (d_stats[VRT_S_RNG_EXHAUSTED]): the capacities of include/vrt.h,
+# vrt_workspace_bytes, restated for the VrtError of render() and render_views() -- keep the two alike
+_EXHAUSTED_RULE = ("they consumed more than 1024 random draws (341 rough hits), or a re-trace list of their march launch (at "
+                   "most 2**28 ray slots of the %s) was full: more than 4096 rays of the launch needed more than 113 draws, or "
+                   "more rays than 1/64 of the launch, held between 2**18 and 2**22 (the whole launch if it is smaller), "
+                   "outran the 64-draw table; lower max_bounces or raise material absorption")
+
 _POW_MEMOS = set()   # (device index, falloff) pairs for which vrt_pow_memo_create has run in this process
 
 
@@ -668,10 +675,8 @@ class Camera:
                         return self.render(thread, pixels=dp, want_image=want_image, want_f32=want_f32,
                                            want_ray_rgba=want_ray_rgba, want_rays=want_rays,
                                            want_traversed=want_traversed, seed_nonce=int(st.seed_nonce), check=check)
-                    raise nat.VrtError("%d rays could not be completed: they consumed more than 1024 random draws (341 "
-                                       "rough hits), more than 4096 rays of the frame needed more than 113, or more "
-                                       "than 1/8 of the frame outran the 64-draw table; lower max_bounces or raise "
-                                       "material absorption" % int(res.stats[nat.S_RNG_EXHAUSTED]))
+                    raise nat.VrtError("%d rays could not be completed: %s"
+                                       % (int(res.stats[nat.S_RNG_EXHAUSTED]), _EXHAUSTED_RULE % "frame"))
                 if res.stats[nat.S_STALLED]:
                     raise nat.VrtError("%d waves of the march found nothing to run and gave up (internal error, frame "
                                        "invalid)" % int(res.stats[nat.S_STALLED]))
@@ -834,8 +839,8 @@ class Camera:
                         self.fast_draws = 64
                         return self.render_views(rec[:, :7], thread, pixels=dp, want_image=want_image, want_f32=want_f32,
                                                  want_ray_rgba=want_ray_rgba, want_traversed=want_traversed, check=check)
-                    raise nat.VrtError("%d rays of the batch could not be completed: they outran every draw table; lower "
-                                       "max_bounces or raise material absorption" % int(hstats[nat.S_RNG_EXHAUSTED]))
+                    raise nat.VrtError("%d rays of the batch could not be completed: %s"
+                                       % (int(hstats[nat.S_RNG_EXHAUSTED]), _EXHAUSTED_RULE % "batch"))
                 if hstats[nat.S_TRAV_OUTSIDE]:
                     raise nat.VrtError("%d chunk visits fell outside the traversed boxes (internal bound violated)"
                                        % int(hstats[nat.S_TRAV_OUTSIDE]))
