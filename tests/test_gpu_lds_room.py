@@ -21,7 +21,8 @@ import pytest
 import oracle_lib as ol
 from gpu_util import (BUDGET_LDS, POOL_LDS, STATIC_LDS, active, camera_for, check_frame_march, march_dyn_lds, run_children,
                       settings_store)
-from test_gpu_edges import CNT, RAY_FIELDS, voxel_ids_at
+from edge_scenes import CNT, voxel_ids_at
+from test_gpu_edges import RAY_FIELDS
 
 pytestmark = pytest.mark.gpu
 

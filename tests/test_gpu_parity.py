@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
+from edge_scenes import BOUNDARY_POSITIONS, BOUNDARY_RES_CAPS, boundary_scene
 from gpu_util import (active, bitmap_window, camera_for, check_frame_march, check_tile_plan, settings_store, sparse_scene,
                       window_split)
 
@@ -671,30 +672,16 @@ def test_random_scenes_bit_exact(seed, frame_march):
     check_frame_march(cam, o, cs, frame_march)
 
 
-@pytest.mark.parametrize("pos", [(0.0, 0.0, 0.0), (16.0, 16.0, 16.0), (8.0, 16.0, -16.0), (-0.0, 5.0, -5.0), (-16.0, 0.0, 31.0),
-                                 (1e-300, -1e-300, 15.999999999999998), (32.0, -32.0, 0.5)])
+@pytest.mark.parametrize("pos", BOUNDARY_POSITIONS)
 def test_axis_aligned_rays_from_integer_and_boundary_cameras(pos, frame_march):
     """The integer forms of the march's box tests (floor by magic add, `floor(p) - chunk_min in [0, cs)` or `== cs` with p
     integral, the first-snap special case p == (0, 0, 0)) on the inputs that sit exactly on their edges: unrotated camera,
     no jitter, dist_min 0, even image size -- the centre column / row rays move along the axes planes with coordinates that
-    stay integers, the camera sits on chunk corners, faces, the origin and one ulp beside them.  Both kernels (the
-    recording one and the frame march) against the oracle, resolutions 1..3."""
-    rng = np.random.default_rng(12345)
-    cs = 16
-    dims = np.array([4, 4, 4])
-    origin = np.array([-32, -32, -32], np.int64)
-    present = (rng.random(tuple(dims)) < 0.85).astype(np.uint8)
-    res = rng.integers(1, 4, tuple(dims)).astype(np.uint8)
-    mats = np.array([[200, 40, 40, 0.0, 0.5, 0.0, 0.0], [40, 200, 40, 0.5, 1.0, 0.75, 0.0], [40, 40, 200, 0.1, 0.25, 0.25, 0.5],
-                     [220, 220, 220, 1.0, 2.0, 1.0, 0.0]])
-    grid = np.where(rng.random(tuple(dims * cs)) < 0.08, rng.integers(1, 5, tuple(dims * cs)), 0).astype(np.uint8)
-    for rm in (1, 3):                                   # resolutions <= 1 only (RESMODE 0 kernel) and up to 3
-        r_ = np.minimum(res, rm).astype(np.uint8)
-        sc = ol.Scene(origin, dims, cs, present, r_, ol.Scene.camera_grid(grid, origin, dims, cs, present, r_), mats)
-        st = ol.make_settings(width=32, height=24, samples=2, max_bounces=4.0, chunk_size=cs, dist_max=96, dist_min=0,
-                              dof=0.0, lod_edge=0.0, lod_random=0.0, lod_samples=0.0, fov=90.0)
-        q = np.array([0.0, 0.0, 0.0, 1.0])
-        lens = st["fov"] * np.pi / 8
+    stay integers, the camera sits on chunk corners, faces, the origin and one ulp beside them (tests/edge_scenes.py:
+    boundary_scene).  Both kernels (the recording one and the frame march) against the oracle, resolutions 1..3."""
+    for rm in BOUNDARY_RES_CAPS:                        # resolutions <= 1 only (RESMODE 0 kernel) and up to 3
+        sc, st, q, lens = boundary_scene(rm)
+        cs = sc.chunk_size
         cam = camera_for(sc, settings_store(st), np.array(pos), q, lens)
         r = cam.render(0, want_rays=True)
         o = ol.render(sc, st, np.array(pos), q, lens, r.pixels, libm=ol.LIBM_PORTABLE)

@@ -409,3 +409,82 @@ def test_device_world_update_keeps_the_reference_merge_order():
         assert rebuilt > 0
         assert [objs.index(o) for o in dw._order] == seq["order_" + tag].tolist()
         check(tag)
+
+
+# ---------------------------------------------------------------------------------------- 64 objects, every quarter turn
+def build_from_random_fixture(z):
+    """The objects of tests/golden/world_random.npz (tests/golden/make_world_random.py) from its spec: models from the stored
+    voxel lists, positions and angles as the reference was given them.  Returns (materials, settings, objects)."""
+    mats = [Material(function=material, albedo=rgb(*[int(v) for v in row[:3]]), roughness=row[3], absorption=row[4],
+                     ior=row[5], energy=row[6]) for row in z["materials"]]
+    s = json.loads(bytes(z["settings"]).decode())
+    st = make_settings(**{k: s[k] for k in ("width", "height", "samples", "max_bounces", "dist_max", "chunk_lod")})
+    st.culling = False
+    cam_pos = vec3(*[float(v) for v in z["cam_pos"]])
+    num = lambda v: float(v) if v % 1 else int(v)  # noqa: E731
+    objs = []
+    for k, (size, lod, pos, rot) in enumerate(zip(z["spec_size"], z["spec_lod"], z["spec_pos"], z["spec_rot"])):
+        spr = Sprite(size=vec3(*[num(v) for v in size]), frames=1, lod=int(lod))
+        rows = z["vox"][int(z["vox_start"][k]):int(z["vox_start"][k + 1])]
+        spr.get_frame(0).set_voxels({(int(x), int(y), int(c)): mats[int(m)] for x, y, c, m in rows}, True)
+        ob = Object(pos=vec3(*[num(v) for v in pos]), rot=vec3(*[num(v) for v in rot]), sprite=spr)
+        ob.update(cam_pos, st)
+        objs.append(ob)
+    return mats, st, objs
+
+
+def random_fixture():
+    z = np.load(os.path.join(ol.GOLDEN, "world_random.npz"))
+    # what the generator refused to write the file without: turns that apply, turns the size rule ignores, contested voxels
+    assert len(z["spec_rot"]) == 64 and int(z["turns_effective"]) >= 40 and int(z["turns_ignored"]) >= 10 and int(z["contested"]) >= 20
+    return z
+
+
+def _on_box(origin, grid, lo, hi, fill):
+    """`grid` (lowest corner `origin`) copied into a box [lo, hi) filled with `fill`."""
+    out = np.full(tuple(hi - lo), fill, grid.dtype)
+    o = np.asarray(origin, np.int64) - lo
+    out[o[0]:o[0] + grid.shape[0], o[1]:o[1] + grid.shape[1], o[2]:o[2] + grid.shape[2]] = grid
+    return out
+
+
+def test_random_world_boxes_and_visibility_match_reference():
+    """Sprite sizes, the integer boxes of fractional positions (ceil / floor, data.py:596-597) and visibility by distance
+    (data.py:569) of all 64 objects are the reference's."""
+    z = random_fixture()
+    mats, st, objs = build_from_random_fixture(z)
+    assert np.array_equal([[o.sprite.size.x, o.sprite.size.y, o.sprite.size.z] for o in objs], z["sprite_size"])
+    assert np.array_equal([[o.mins.x, o.mins.y, o.mins.z] for o in objs], z["obj_mins"])
+    assert np.array_equal([[o.maxs.x, o.maxs.y, o.maxs.z] for o in objs], z["obj_maxs"])
+    assert np.array_equal([bool(o.visible) for o in objs], z["obj_visible"]) and not z["obj_visible"].all()
+
+
+def test_random_world_voxels_match_reference():
+    """build_world over one object per quarter-turn triple -- cubes, boxes with two equal extents on each axis and boxes with
+    none, sprite LOD 0 and 1, angles that only round-half-even maps to their turn -- gives the reference's voxels."""
+    z = random_fixture()
+    mats, st, objs = build_from_random_fixture(z)
+    turns = {tuple(round(float(a) / 90) % 4 for a in rot) for rot in z["spec_rot"]}
+    assert len(turns) == 64 and {45.0, 135.0, -45.0} <= set(z["spec_rot"].reshape(-1).tolist())
+    w = build_world(objs, 16)
+    remap = np.zeros(len(w.materials) + 1, np.uint8)
+    for k, m in enumerate(w.materials):
+        remap[k + 1] = 1 + mats.index(m)
+    assert int((z["grid_lod0"] != 0).sum()) > 4000
+    assert _same_voxels(w.origin, remap[w.grid], z["origin"], z["grid_lod0"])
+    assert int(w.present.sum()) == int(z["present"].sum())
+
+
+def test_random_world_owners_match_reference():
+    """build_world(owners=True): WHICH object every voxel came from is the reference's own (its chunks_objects dict walked in
+    order, the last holder wins), over a world in which hundreds of voxels are held by two objects."""
+    z = random_fixture()
+    mats, st, objs = build_from_random_fixture(z)
+    w = build_world(objs, 16, owners=True)
+    spec_index = np.array([k for k, o in enumerate(objs) if o.visible] + [-1])     # (owner -1 -> -1)
+    lo = np.minimum(w.origin, z["origin"])
+    hi = np.maximum(w.origin + w.grid.shape, z["origin"] + z["owner"].shape)
+    got = _on_box(w.origin, spec_index[w.owner], lo, hi, -1)
+    exp = _on_box(z["origin"], z["owner"].astype(np.int64), lo, hi, -1)
+    assert np.array_equal(got, exp), int((got != exp).sum())
+    assert len(np.unique(exp[exp >= 0])) == 63
