@@ -373,6 +373,48 @@ typedef struct vrt_cast_ray {   /* 64 bytes, 64-byte aligned array */
 int vrt_cast_rays(const vrt_scene* scene, const vrt_settings* st, const vrt_cast_ray* d_rays, int64_t n_rays,
                   double max_life, vrt_hit* d_hits, uint64_t* d_stats, void* stream);
 
+/* ---- shaded explicit rays -------------------------------------------------------------------------------
+ * What colour and energy arrive along rays that come from no camera pixel: an orthographic or top-down map view, light
+ * probes, a mirror or portal pass that starts at first-hit records, a fisheye or cube-map lens, a range sensor that wants
+ * the shaded return.  vrt_cast_rays's rays (the same 64-byte vrt_cast_ray records, the same validation, the same max_life)
+ * through the whole of Camera.trace's loop.
+ *   Start state.  Ray i starts in the state of init.py:50-59 with the caller's doubles: pos = origin, vel = vel, life = life;
+ *             step = bounces = energy = 0, colour (0, 0, 0), no current chunk.  The library does no arithmetic on origin,
+ *             vel or life.
+ *   What runs.  init.py:66-116 -- re-snap, lookup, lib.material, the termination tests, the per-axis reflection from three
+ *             neighbours, the step -- then lib.material_background if st->has_background and
+ *             alpha = round(min(1, energy + shutter) * 255) (init.py:119-120, 141).  Every output is bit for bit what the
+ *             renderer's ray gives from that state.
+ *   Draws.    The k-th random.random() ray i consumes is d_draws[i * n_draws + k], from k = 0: there are no lens or
+ *             lod_random draws, they belong to Camera.tile.  n_draws = 0 with d_draws = NULL is legal (a ray that meets a
+ *             rough material then runs out at once).
+ *   st        supplies chunk_size, chunk_radius, has_background, shutter, falloff, max_light, max_bounces and lod_bounces
+ *             (and is checked like every settings block); dist_min, dist_max, dof, lod_samples, lod_random, lod_edge, samples,
+ *             width, height and proportions are not read.
+ *   Rejection.  Exactly vrt_cast_rays's rule (see vrt_cast_ray), per ray on the device.  A rejected ray is never marched:
+ *             d_rgba[i] = 0, d_records[i].s = -2 and every other field of the record 0, counted in
+ *             d_stats[VRT_S_CAST_REJECTED].
+ *   Exhaustion.  A ray that needs more draws than n_draws is not completed: d_rgba[i] = 0, d_records[i].s = -3 and every
+ *             other field 0, counted in d_stats[VRT_S_RNG_EXHAUSTED] and not in d_stats[VRT_S_RAYS] -- the records alone
+ *             tell which rays to repeat with a longer row.
+ *   d_rgba    [n_rays] uint32 r | g << 8 | b << 16 | alpha << 24, or NULL.
+ *   d_records [n_rays] vrt_ray, or NULL (not both): a completed ray has x = y = s = 0 and detail = 1.0; colour, alpha, energy,
+ *             step, life, bounces, pos and vel are its end state; ntrav counts its distinct chunks; the counters are those
+ *             vrt_trace_rays writes, counters[VRT_C_DRAW] the draws consumed.  (Records cost speed, as in vrt_render_tile.)
+ *   d_stats   [VRT_NSTATS] uint64, zeroed by the callee: [0..7] event sums over completed rays, [8] completed rays,
+ *             [9] rejected, [10] exhausted, [11] chunk visits outside the traversed box, [12..15] 0.
+ *   trav      NULL, or a box with vrt_render_tile's key rule: ray index << 12 | resnap index; `reset` is honoured.  With
+ *             culling on, a chunk that only a map view or a mirror sees would otherwise be dropped by the next selection.
+ *   d_workspace: vrt_shade_workspace_bytes() bytes -- the launch-wide ray counter and a pow memo for frames whose falloff has
+ *             no table of vrt_pow_memo_create's (which is used when present, as in vrt_trace_rays); nothing per ray.
+ * n_rays = 0 only zeroes the statistics; n_rays >= 2^32 - 1 is VRT_ERR_ARG; more than 2^28 rays are split into launches.
+ * Every argument is checked before any HIP call; nothing is allocated or synchronised, so a call may be captured into a
+ * hipGraph.  Not offered: averaging several samples per ray, the ray pool (one ray per lane: march_kernel's schedule). */
+int vrt_shade_workspace_bytes(int64_t n_rays, int64_t* bytes);
+int vrt_shade_rays(const vrt_scene* scene, const vrt_settings* st, const vrt_cast_ray* d_rays, int64_t n_rays,
+                   double max_life, const double* d_draws, int32_t n_draws, void* d_workspace, int64_t workspace_bytes,
+                   uint32_t* d_rgba, vrt_ray* d_records, uint64_t* d_stats, const vrt_traversed* trav, void* stream);
+
 /* Camera.trace (init.py:37-121) for explicit rays: direction (dir_x, dir_y), detail and the random draws the
  * ray may consume (d_draws[i * n_draws + k] = k-th random.random() of ray i).  d_rays[i].counters[VRT_C_DRAW]
  * tells how many were consumed.  Rays that would need more draws are counted in d_stats[VRT_S_RNG_EXHAUSTED].

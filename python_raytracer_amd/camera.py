@@ -202,6 +202,64 @@ class CastResult:
         return self.material == nat.HIT_REJECTED
 
 
+class ShadeResult:
+    """Device-side outputs of Camera.shade_rays: what colour and energy arrived along every explicit ray.  `rgba` is packed
+    r | g << 8 | b << 16 | alpha << 24, entry k for ray k; `records` (or None) one buffer of 152-byte vrt_ray records
+    (include/vrt.h), whose `s` field is 0 for a completed ray, -2 for a rejected one and -3 for one whose draws ran out."""
+
+    def __init__(self, rgba, records, stats_dev, trav=None):
+        self.rgba = rgba                 # uint32 [n]
+        self.records = records           # uint8 [n * 152], or None
+        self._stats_dev = stats_dev
+        self._stats = None
+        self.traversed_keys, self.trav_origin, self.trav_dims = trav if trav is not None else (None, None, None)
+
+    @property
+    def stats(self):
+        """numpy int64[16], copied from the device on first use (a synchronisation): words 0..7 event sums over completed
+        rays, 8 completed rays, 9 rejected, 10 rays whose draws ran out, 11 chunk visits outside the traversed box."""
+        if self._stats is None:
+            self._stats = self._stats_dev.cpu().numpy()
+        return self._stats
+
+    def _s(self, what):
+        import torch
+        if self.records is None:
+            raise ValueError("%s needs the records (shade_rays(..., want_records=True))" % what)
+        n = self.records.numel() // nat.RAY_BYTES
+        return self.records.view(torch.int32).view(n, nat.RAY_BYTES // 4)[:, 2]
+
+    def numpy(self):
+        """The records as a numpy structured array of vrt_ray (fields x, y, s, color, alpha, ntrav, counters, detail,
+        energy, step, life, bounces, pos, vel)."""
+        if self.records is None:
+            raise ValueError("numpy() needs the records (shade_rays(..., want_records=True))")
+        return self.records.cpu().numpy().view(np.dtype(nat.RAY_FIELDS, align=True))
+
+    def rejected_mask(self):
+        """torch.bool [n]: the ray was rejected on the device (cast_rays's rule) and was not marched."""
+        return self._s("rejected_mask()") == nat.RAY_REJECTED
+
+    def exhausted_mask(self):
+        """torch.bool [n]: the ray needed more draws than it was given and was not completed: repeat it with a longer row."""
+        return self._s("exhausted_mask()") == nat.RAY_EXHAUSTED
+
+    def image(self, height, width):
+        """[height, width, 4] uint8 RGBA from n == height * width rays in row-major order (ray y * width + x is pixel (x, y))."""
+        import torch
+        height, width = int(height), int(width)
+        if height <= 0 or width <= 0 or height * width != int(self.rgba.numel()):
+            raise ValueError("image(%d, %d): %d rays are not %d x %d pixels" % (height, width, int(self.rgba.numel()), height, width))
+        return self.rgba.view(torch.uint8).view(height, width, 4)
+
+    def traversed(self, chunk_size):
+        """Visited chunk positions inside the box the call was given, in the reference's order (the order-preserving union
+        over the rays in array order); [] without a box."""
+        rr = RenderResult()
+        rr.traversed_keys, rr.trav_origin, rr.trav_dims = self.traversed_keys, self.trav_origin, self.trav_dims
+        return rr.traversed(chunk_size)
+
+
 class Camera:
     def __init__(self, settings=None, device=None):
         import torch
@@ -963,8 +1021,8 @@ class Camera:
                 for v in range(n_views)]
 
     # ------------------------------------------------------------------ explicit rays: the first voxel along any ray
-    def _cast_records(self, origins, velocities, lives, default_life):
-        """[n, 8] float64 device tensor of vrt_cast_ray records from what cast_rays was given."""
+    def _cast_records(self, origins, velocities, lives, default_life, who="cast_rays"):
+        """[n, 8] float64 device tensor of vrt_cast_ray records from what cast_rays (or shade_rays: `who`) was given."""
         torch = self._torch
         dev = self._require_device()
 
@@ -974,31 +1032,31 @@ class Camera:
         if velocities is None:
             # ready records, used as they are
             if not is_t(origins) or origins.dtype != torch.float64 or not origins.is_cuda:
-                raise ValueError("cast_rays(records): the records must be one float64 CUDA tensor [n, 8]")
+                raise ValueError(who + "(records): the records must be one float64 CUDA tensor [n, 8]")
             if origins.dim() != 2 or origins.shape[1] != 8 or not origins.is_contiguous() or origins.data_ptr() % 64:
-                raise ValueError("cast_rays(records): the records must be a contiguous, 64-byte aligned [n, 8] tensor")
+                raise ValueError(who + "(records): the records must be a contiguous, 64-byte aligned [n, 8] tensor")
             if origins.device != dev:
-                raise ValueError("cast_rays(records): the records are on %s, the camera renders on %s" % (origins.device, dev))
+                raise ValueError(who + "(records): the records are on %s, the camera renders on %s" % (origins.device, dev))
             if lives is not None:
-                raise ValueError("cast_rays(records): ready records carry their own lives")
+                raise ValueError(who + "(records): ready records carry their own lives")
             return origins
         parts = []
         for name, v in (("origins", origins), ("velocities", velocities)):
             if is_t(v):
                 if not v.dtype.is_floating_point:
-                    raise ValueError("cast_rays: %s must be floating point, not %s" % (name, v.dtype))
+                    raise ValueError(who + ": %s must be floating point, not %s" % (name, v.dtype))
                 v = v.to(device=dev, dtype=torch.float64)
             else:
                 a = np.asarray(v)
                 if a.dtype.kind not in "fiu":
-                    raise ValueError("cast_rays: %s must be numbers, not %s" % (name, a.dtype))
+                    raise ValueError(who + ": %s must be numbers, not %s" % (name, a.dtype))
                 v = torch.from_numpy(np.array(a, np.float64)).to(dev)
             if v.dim() != 2 or v.shape[1] != 3:
-                raise ValueError("cast_rays: %s must have shape [n, 3], not %s" % (name, list(v.shape)))
+                raise ValueError(who + ": %s must have shape [n, 3], not %s" % (name, list(v.shape)))
             parts.append(v)
         n = int(parts[0].shape[0])
         if int(parts[1].shape[0]) != n:
-            raise ValueError("cast_rays: %d origins but %d velocities" % (n, int(parts[1].shape[0])))
+            raise ValueError(who + ": %d origins but %d velocities" % (n, int(parts[1].shape[0])))
         rec = torch.zeros((n, 8), dtype=torch.float64, device=dev)
         rec[:, 0:3] = parts[0]
         rec[:, 3:6] = parts[1]
@@ -1008,7 +1066,7 @@ class Camera:
             lv = lives.to(device=dev, dtype=torch.float64) if is_t(lives) else \
                 torch.from_numpy(np.array(lives, np.float64)).to(dev)
             if lv.dim() != 1 or int(lv.shape[0]) != n:
-                raise ValueError("cast_rays: lives must have shape [%d], not %s" % (n, list(lv.shape)))
+                raise ValueError(who + ": lives must have shape [%d], not %s" % (n, list(lv.shape)))
             rec[:, 6] = lv
         return rec
 
@@ -1051,6 +1109,129 @@ class Camera:
                                  torch.cuda.current_stream().cuda_stream)
             nat.check(rc, "vrt_cast_rays")
         return CastResult(records, stats)
+
+    # ------------------------------------------------------------------ explicit rays: colour and end state along any ray
+    def _shade_box(self, want):
+        """The traversed box of shade_rays: False / None none; True the camera's own (_trav_box: around cam.pos, sized for
+        dist_max); or (origin, dims) -- world coordinates of cell (0, 0, 0), multiples of chunk_size, and cells per axis."""
+        torch = self._torch
+        if want is None or want is False or want is True:
+            return self._trav_box(bool(want))
+        origin, dims = want
+        origin, dims = [int(v) for v in origin], [int(v) for v in dims]
+        cs = int(self._settings().chunk_size)
+        if len(origin) != 3 or len(dims) != 3 or any(o % cs for o in origin) or any(d <= 0 for d in dims):
+            raise ValueError("shade_rays: want_traversed=(origin, dims) takes an origin in multiples of chunk_size and positive "
+                             "dims, not %r" % (want,))
+        if dims[0] * dims[1] * dims[2] > (1 << 28):
+            raise ValueError("shade_rays: the traversed box %r has more than 2**28 cells" % (dims,))
+        tr = nat.VrtTraversed()
+        keys = torch.empty((dims[0] * dims[1] * dims[2],), dtype=torch.int64, device=self._device)
+        tr.origin[:] = origin
+        tr.dims[:] = dims
+        tr.reset = 1
+        tr.d_keys = keys.data_ptr()
+        return tr, keys
+
+    def shade_rays(self, origins, velocities=None, lives=None, *, seeds=None, draws=None, n_draws=None, max_life=None,
+                   want_records=True, want_traversed=False, stream=None):
+        """Colour and end state along explicit rays (vrt_shade_rays): ray k starts at origins[k] with velocity velocities[k]
+        and life lives[k] -- the state of init.py:50-59 -- and runs the whole of Camera.trace's loop from there (hits,
+        lib.material, reflection, lib.material_background if the camera has a background, the alpha): bit for bit what the
+        renderer's ray gives from that state.  The rays go against the scene this camera currently renders; the camera's own
+        pose, lens, dist_min / dist_max, dof and lod settings play no part.
+        origins, velocities, lives, max_life: as cast_rays takes them (numpy or torch, or ONE ready [n, 8] float64 CUDA
+        tensor), with the same rejection rule.
+        seeds: [n] integers in [0, 2**63): ray k's draws are random.seed(seeds[k]) followed by random.random() repeatedly,
+        n_draws of them (default 32, 2..4096), made on the device (vrt_rng_draws).  numpy seeds are range-checked; a torch
+        tensor is taken as it is (checking it would synchronise): a negative value there is read as its unsigned 64-bit
+        pattern.  draws: [n, n_draws] float64, used as
+        given.  Neither: no draws -- a ray that meets a rough material runs out at once.  A ray that needs more draws than it
+        has is not completed: rgba 0, record s = -3 (exhausted_mask()), counted in stats[10].
+        want_traversed: True for the camera's own box (around cam.pos, sized for dist_max), or (origin, dims) for a box of
+        the caller's -- origin: world coordinates of cell (0, 0, 0), multiples of chunk_size; dims: cells per axis, at most
+        2**28 in all; visits outside it are counted in stats[11] -- a map view or a mirror
+        sees chunks the camera's rays do not, and with culling on the next chunk_update() would drop them.
+        Returns a ShadeResult of device tensors; nothing is copied to the host and nothing synchronises (with tensors already
+        on the device the call can be captured into a graph)."""
+        torch = self._torch
+        L = nat.lib()
+        dev = self._require_device()
+        s = self._settings()
+        if max_life is None:
+            max_life = float(s.dist_max)
+        max_life = float(max_life)
+        if not (max_life > 0) or max_life > float(1 << 28):
+            raise ValueError("shade_rays: max_life must lie in (0, 2**28], not %r" % max_life)
+        if seeds is not None and draws is not None:
+            raise ValueError("shade_rays: pass seeds or draws, not both")
+        if seeds is not None:
+            n_draws = 32 if n_draws is None else int(n_draws)
+            if not 2 <= n_draws <= 4096:
+                raise ValueError("shade_rays: n_draws must lie in 2..4096, not %r" % n_draws)
+        sc = self._ensure_scene()
+        st = self._c_settings(0)
+        if not torch.cuda.is_current_stream_capturing():
+            _ensure_pow_memo(torch, dev, s.falloff)
+        with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            rec = self._cast_records(origins, velocities, lives, float(s.dist_max) - float(s.dist_min), "shade_rays")
+            n = int(rec.shape[0])
+            if n == 0:
+                raise ValueError("shade_rays: no rays")
+            if n >= (1 << 32) - 1:
+                raise ValueError("shade_rays: 2**32 - 1 rays and more need several calls")
+            cur = torch.cuda.current_stream().cuda_stream
+            if seeds is not None:
+                if isinstance(seeds, torch.Tensor):
+                    if seeds.dtype.is_floating_point or seeds.dtype == torch.bool:
+                        raise ValueError("shade_rays: seeds must be integers, not %s" % seeds.dtype)
+                    sd = seeds.to(device=dev, dtype=torch.int64)
+                else:
+                    a = np.asarray(seeds)
+                    if a.dtype.kind not in "iu" or (a.size and (int(a.min()) < 0 or int(a.max()) >= 1 << 63)):
+                        raise ValueError("shade_rays: seeds must be integers in [0, 2**63)")
+                    sd = torch.from_numpy(np.array(a, np.int64)).to(dev)
+                if sd.dim() != 1 or int(sd.shape[0]) != n:
+                    raise ValueError("shade_rays: seeds must have shape [%d], not %s" % (n, list(sd.shape)))
+                sd = sd.contiguous()
+                dd = torch.empty((n, n_draws), dtype=torch.float64, device=dev)
+                nat.check(L.vrt_rng_draws(sd.data_ptr(), n, n_draws, dd.data_ptr(), cur), "vrt_rng_draws")
+            elif draws is not None:
+                if isinstance(draws, torch.Tensor):
+                    if not draws.dtype.is_floating_point:
+                        raise ValueError("shade_rays: draws must be floating point, not %s" % draws.dtype)
+                    dd = draws.to(device=dev, dtype=torch.float64)
+                else:
+                    a = np.asarray(draws)
+                    if a.dtype.kind not in "fiu":
+                        raise ValueError("shade_rays: draws must be numbers, not %s" % a.dtype)
+                    dd = torch.from_numpy(np.array(a, np.float64)).to(dev)
+                if dd.dim() != 2 or int(dd.shape[0]) != n or (n_draws is not None and int(dd.shape[1]) != int(n_draws)):
+                    raise ValueError("shade_rays: draws must have shape [%d, %s], not %s"
+                                     % (n, "n_draws" if n_draws is None else int(n_draws), list(dd.shape)))
+                dd = dd.contiguous()
+                n_draws = int(dd.shape[1])
+            else:
+                dd, n_draws = None, 0
+            csc = self._c_scene(sc)
+            tr, keys = self._shade_box(want_traversed)
+            rgba = torch.empty(n, dtype=torch.uint32, device=dev)
+            records = torch.empty(n * nat.RAY_BYTES, dtype=torch.uint8, device=dev) if want_records else None
+            stats = torch.empty(nat.NSTATS, dtype=torch.int64, device=dev)   # (the library clears it)
+            nb = C.c_int64(0)
+            nat.check(L.vrt_shade_workspace_bytes(n, C.byref(nb)), "vrt_shade_workspace_bytes")
+            # (a workspace of the call's own, kept by the result: it holds the launch-wide ray counter, and a captured call
+            # keeps its pointer -- the camera's per-stream workspace is replaced when a later frame needs a larger one)
+            ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+            rc = L.vrt_shade_rays(C.byref(csc), C.byref(st), rec.data_ptr(), n, max_life,
+                                  dd.data_ptr() if n_draws else None, n_draws, ws.data_ptr(), ws.numel(), rgba.data_ptr(),
+                                  records.data_ptr() if want_records else None, stats.data_ptr(),
+                                  C.byref(tr) if keys is not None else None, cur)
+            nat.check(rc, "vrt_shade_rays")
+        trav = (keys, [int(v) for v in tr.origin], [int(v) for v in tr.dims]) if keys is not None else None
+        res = ShadeResult(rgba, records, stats, trav)
+        res._workspace = ws
+        return res
 
     def line_of_sight(self, a, b, stream=None):
         """torch.bool [n]: can point a[k] see point b[k]?  One cast per pair: vel = (b - a) / max|b - a| -- the reference's

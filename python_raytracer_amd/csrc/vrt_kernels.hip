@@ -2338,7 +2338,8 @@ __device__ __forceinline__ void hit_body(const MarchParams& P, const MarchCtx& C
 // ENDED: lib.material_background (lib.py:463-476), tile()'s alpha (init.py:141), the ray's outputs.  PERRAY: `cnt` holds
 // this ray's events and joins the totals here; else the lane counts events of all its rays in `cnt` itself and only the
 // per-ray words (re-snaps, draws, broke) are added.  A ray whose draws ran out is queued for the re-trace instead.
-template <bool RECORD, bool PERRAY>
+// EXPLICIT (shade_kernel): the ray came from no pixel and no detail array -- its record has x = y = s = 0 and detail 1.
+template <bool RECORD, bool PERRAY, bool EXPLICIT = false>
 __device__ __forceinline__ void ended_body(const MarchParams& P, const MarchCtx& C, const Ray& r, int state, const int32_t (&cnt)[C_NLOCAL],
                                            int nseen, unsigned long long* s_stats) {
     (void)nseen;
@@ -2368,7 +2369,11 @@ __device__ __forceinline__ void ended_body(const MarchParams& P, const MarchCtx&
         vrt_ray& o = Q.rays[ray];
         int x = 0, y = 0, s = 0;
         double detail;
-        if (C.tile) {
+        if constexpr (EXPLICIT) {
+            detail = 1.0;
+            x = y = s = opaque_zero();  // (made where they are stored: as constants the three zeroes are hoisted out of the
+                                        // kernel's loop into vector registers of their own, and spilled)
+        } else if (C.tile) {
             const int64_t p = ray / Q.g.smax;
             s = (int)(ray - p * Q.g.smax);
             x = Q.g.pixels[2 * p];
@@ -2425,7 +2430,9 @@ struct MarchSharedT {  // static LDS of a march workgroup (W: the per-axis offse
 };
 typedef MarchSharedT<false> MarchShared;
 // dynamic LDS: materials | chunk table | settled bitmap [| brick slots of lookup variant 2 | ray pool]
-template <bool W = false>
+// TD_ARGS (shade_kernel's generic-resolution instances): the traversed box's dimensions are not pinned to vector registers
+// (MarchCtx::td) -- the kernel has none to spare and would spill them; its re-snaps read them with their other arguments
+template <bool W = false, bool TD_ARGS = false>
 __device__ __forceinline__ void march_prologue(const MarchParams& P, MarchSharedT<W>& S, unsigned char* s_dyn, MarchCtx& C) {
     double* s_mats = reinterpret_cast<double*>(s_dyn);
     uint32_t* s_ct = reinterpret_cast<uint32_t*>(s_dyn + (size_t)P.n_materials * 64);
@@ -2509,7 +2516,7 @@ __device__ __forceinline__ void march_prologue(const MarchParams& P, MarchShared
         C.toc[a] = P.t_origin_c[a];
         C.oc[a] = P.origin_c[a];
         C.dm[a] = P.dims[a];
-        if (!W) asm volatile("" : "+v"(C.td[a]));  // (W: every re-snap reads the dimensions with its other arguments)
+        if (!W && !TD_ARGS) asm volatile("" : "+v"(C.td[a]));  // (W, TD_ARGS: every re-snap reads the dimensions with its other arguments)
     }
 }
 // the workgroup's totals -> the launch's statistics.  Columns are added as signed 32-bit sums: a re-trace launch takes
@@ -2686,8 +2693,8 @@ __device__ __forceinline__ void stage_views(const MarchParams& P, unsigned char*
 // DEFER: see march_step
 // (The lane set-up is shared with the other persistent kernels: ray_clear, lk_unused, seen_unused, DG_LANE above.  The hand-out
 // is HandOut's, written out: with the struct the instances that make their own ray records (PERPIX 3) need 2 more vector
-// registers and every march_pool_kernel instance spills 1-2 more scalar registers.  A fix to HandOut belongs here and in
-// march_pool_kernel's refill too; march_views_kernel and first_hit_kernel use the struct.)
+// registers and every march_pool_kernel instance spills 1-2 more scalar registers.  A fix to HandOut belongs here, in
+// march_pool_kernel's refill and in shade_kernel's too; march_views_kernel, first_hit_kernel and cast_kernel use the struct.)
 template <int SPEC, int RESMODE, bool RECORD, bool LIST, int LK = 0, int PERPIX = (RECORD || LIST) ? 4 : 0, bool W = false, bool DEFER = false, int SEED = 0>
 __global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) march_kernel(MarchParams P) {
     static_assert(SPEC >= 4 && SPEC <= 16, "speculation depth");
@@ -3239,6 +3246,167 @@ __global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) cast_kernel(Mar
         if (n_found) atomicAdd((unsigned long long*)&P.stats[VRT_C_HIT], (unsigned long long)n_found);
         if (n_bad) atomicAdd((unsigned long long*)&P.stats[VRT_S_CAST_REJECTED], (unsigned long long)n_bad);
     }
+}
+
+// ---- shade_kernel: colour and end state along explicit rays (vrt_shade_rays) ---------------------------------------------
+// cast_kernel's rays through march_kernel's loop: record k of the launch is ray ray0 + k of the caller's array, a 64-byte
+// vrt_cast_ray fetched whole and validated (cast_ray_ok) -- a rejected ray is never marched: rgba 0, a record with s = -2,
+// counted in stats[VRT_S_CAST_REJECTED] -- whose origin, velocity and life ARE the state of init.py:50-59.  From there the
+// ray is the renderer's: march_step, hit_body and ended_body as they are, the MARCH / HIT / ENDED state machine with its
+// t_hit / t_end thresholds, the prologue's materials, chunk table, pow memo and offset tables in LDS, the traversed keys
+// with the settled bitmap.  The k-th draw the ray consumes is draws[ray * draw_stride + k] from k = 0 (no lens or lod draws
+// came before: they are Camera.tile's).  A ray whose row runs out is not completed: ended_body counts it in
+// stats[VRT_S_RNG_EXHAUSTED] and writes nothing, so the marker -- rgba 0, a record with s = -3 -- is written here: the
+// caller tells which rays to repeat from the records alone.  No camera is staged (COLD_POS, COLD_ROT, COLD_DIST_MIN are
+// the zeroes of fill_scene_params and nothing reads them).  MarchParams carries the rays where a frame carries its ray
+// table (tab.rec) and the caller's bound on a ray's life in `lens`, as for cast_kernel.
+// (not inlined: its 38 stores in front of both the refill and the ENDED body cost the generic-resolution instances vector
+// registers they do not have)
+__device__ __noinline__ void shade_mark(const __attribute__((address_space(4))) MarchParams& Q, int64_t ray, int s) {
+    if (Q.ray_rgba) Q.ray_rgba[ray] = 0;
+    if (Q.rays) {
+        vrt_ray o = {};
+        o.s = s;
+        Q.rays[ray] = o;
+    }
+}
+template <int SPEC, int RESMODE, bool RECORD>
+__global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) shade_kernel(MarchParams P) {
+    static_assert(SPEC >= 4 && SPEC <= 16, "speculation depth");
+    __shared__ MarchShared S;
+    extern __shared__ __align__(16) unsigned char s_dyn[];
+    MarchCtx C;
+    march_prologue<false, RESMODE == 2>(P, S, s_dyn, C);  // (TD_ARGS: the generic instances would spill MarchCtx::td)
+    C.vw = nullptr;
+    __syncthreads();
+
+    const int wave_in_block = threadIdx.x >> 6;
+    // (the hand-out is HandOut's, written out as in march_kernel: with the struct the generic-resolution instances spill
+    // vector registers)
+    const int64_t count = P.n;
+    const int64_t chunk = P.chunk;
+    int64_t next = 0, range_end = 0;
+    bool more = true;  // the launch-wide counter may still have rays
+    if (chunk == 0) {  // static contiguous range per wave
+        const int64_t n_waves = (int64_t)gridDim.x * (VRT_BLOCK / VRT_WAVE);
+        const int64_t wave = (int64_t)blockIdx.x * (VRT_BLOCK / VRT_WAVE) + wave_in_block;
+        int64_t per = (count + n_waves - 1) / n_waves;
+        per = (per + 7) & ~(int64_t)7;
+        next = wave * per;
+        range_end = next + per < count ? next + per : count;
+        more = false;
+    }
+
+    Ray r;
+    ray_clear(r);
+    int state = LANE_IDLE;
+    uint32_t n_bad = 0;      // wave-uniform: rays rejected
+    int32_t cnt[C_NLOCAL];   // events of the current ray
+#pragma unroll
+    for (int j = 0; j < C_NLOCAL; j++) cnt[j] = 0;
+    SeenList<RECORD> sl;
+    sl.n = 0;
+    uint64_t wmin_key = 0;
+    LkState lk = lk_unused();
+    DG_LANE(dg);
+
+    for (;;) {
+        // ------------------------------------------------------------------ refill idle lanes
+        unsigned long long idle_mask = __ballot(state == LANE_IDLE);
+        while (idle_mask != 0ull && (next < range_end || more)) {
+            if (next >= range_end) {  // take the next chunk (one atomic per wave per chunk)
+                unsigned long long base = 0;
+                if ((threadIdx.x & 63) == 0) base = atomicAdd(P.queue_head, (unsigned long long)chunk);
+                base = wave_first_u64(base);  // (into scalar registers: what is derived from it stays wave-uniform, scalar code)
+                if ((int64_t)base >= count) {
+                    more = false;
+                    break;
+                }
+                next = (int64_t)base;
+                range_end = next + chunk < count ? next + chunk : count;
+            }
+            const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(idle_mask >> 32),
+                                                            __builtin_amdgcn_mbcnt_lo((unsigned)idle_mask, 0u));
+            const int64_t k = next + rank;
+            next += __popcll(idle_mask);
+            bool bad = false;
+            if (state == LANE_IDLE && k < range_end) {
+                const auto& Q = fresh_args(P);
+                const int64_t ray = Q.ray0 + k;
+                // the whole record is fetched at once (one memory round trip), then inspected
+                const CastRecord c = reinterpret_cast<const CastRecord*>(Q.tab.rec)[ray];
+                if (cast_ray_ok(c, Q.lens, C.cs)) {
+                    // init.py:50-59: the caller's doubles are the ray's state
+                    r.px = c.ox; r.py = c.oy; r.pz = c.oz;
+                    r.vx = c.vx; r.vy = c.vy; r.vz = c.vz;
+                    r.life = c.life;
+                    r.step = 0;
+                    r.bounces = 0;
+                    r.energy = 0;
+                    r.color = 0;
+                    // chunk_min = chunk_max = vec3(0, 0, 0), chunk = None (init.py:46-47): see take_ray
+                    r.nm4x = r.nm4y = r.nm4z = (int)0x80000000u;
+                    r.entry = 0;
+                    r.boff = 0;
+                    r.resnaps = 0;
+                    r.off = (uint32_t)k;
+                    r.ndraw = 0;
+                    r.rowi = (uint32_t)ray;
+                    r.d0 = r.d1 = r.d2 = 0.5;
+                    if (3 <= Q.n_draws) {  // the draws of the ray's first rough hit (hit_body asks for the later ones)
+                        const double* row = Q.draws + ray * Q.draw_stride;
+                        r.d0 = row[0];
+                        r.d1 = row[1];
+                        r.d2 = row[2];
+                    }
+                    sl.n = 0;
+#pragma unroll
+                    for (int j = 0; j < C_NLOCAL; j++) cnt[j] = 0;
+                    state = LANE_MARCH;
+                } else {
+                    shade_mark(Q, ray, -2);  // rejected: reported, never marched
+                    bad = true;
+                }
+            }
+            n_bad += (uint32_t)__popcll(__ballot(bad));
+            idle_mask = __ballot(state == LANE_IDLE);
+        }
+        if (__ballot(state != LANE_IDLE) == 0ull) break;  // range exhausted and every lane finished
+        if (C.has_bm) {  // (see march_kernel)
+            if ((threadIdx.x & 63) == 0) S.wtmp[wave_in_block] = 0xffffffffu;
+            if (state != LANE_IDLE) atomicMin(&S.wtmp[wave_in_block], (uint32_t)(P.ray0 + r.off));
+            wmin_key = publish_wave_min(S, wave_in_block, S.wtmp[wave_in_block]);
+        }
+
+        // ------------------------------------------------------------------ MARCH steps (phase A)
+        int iters = 0;
+        for (;;) {
+            const int n_march = (int)__popcll(__ballot(state == LANE_MARCH));
+            const int n_hit = (int)__popcll(__ballot(state == LANE_HIT));
+            const int n_end = (int)__popcll(__ballot(state >= LANE_ENDED));
+            if (n_march == 0 || n_hit >= P.t_hit || n_end >= P.t_end) break;
+            if (iters >= P.max_iters && n_hit + n_end > 0) break;
+            iters++;
+            if (state == LANE_MARCH) march_step<SPEC, RESMODE, RECORD, 0>(P, C, r, state, cnt, wmin_key, lk, sl, dg);
+        }
+        const bool none_marching = __ballot(state == LANE_MARCH) == 0ull;
+        const bool capped = iters >= P.max_iters;
+
+        // ------------------------------------------------------------------ HIT (phase B: init.py:78-116)
+        const bool serve_hit = none_marching || capped || (int)__popcll(__ballot(state == LANE_HIT)) >= P.t_hit;
+        if (serve_hit && state == LANE_HIT) hit_body<RESMODE, false>(P, C, r, state, cnt, dg);
+
+        // ------------------------------------------------------------------ ENDED: background, outputs
+        const bool serve_ended = none_marching || capped || (int)__popcll(__ballot(state >= LANE_ENDED)) >= P.t_end ||
+                                 __ballot(state == LANE_MARCH) == 0ull;
+        if (serve_ended && state >= LANE_ENDED) {
+            if (state == LANE_ENDED_EXHAUSTED) shade_mark(fresh_args(P), fresh_args(P).ray0 + r.off, -3);
+            ended_body<RECORD, true, true>(P, C, r, state, cnt, sl.n, S.stats);
+            state = LANE_IDLE;
+        }
+    }
+    if ((threadIdx.x & 63) == 0 && n_bad) atomicAdd(&S.stats[VRT_S_CAST_REJECTED], (unsigned long long)n_bad);
+    march_epilogue<false>(P, S);
 }
 
 // ---- march_pool_kernel: the same bodies, rays regrouped between the lanes of a wave through LDS ------------------------
@@ -4486,12 +4654,13 @@ int vrt_workspace_bytes(const vrt_settings* st, int64_t n_px, int64_t n_distinct
 
 static inline bool within(double v, double lim) { return __builtin_fabs(v) <= lim; }  // false for NaN
 
-// The scene half of a launch's parameters, and the camera half where there is a camera: `cam` is NULL for vrt_cast_rays,
-// whose rays come from no camera -- their range is checked ray by ray on the device (cast_ray_ok) -- and which records no
-// traversed list.
+// The scene half of a launch's parameters, and the camera half where there is a camera: `cam` is NULL for vrt_cast_rays
+// and vrt_shade_rays, whose rays come from no camera -- their range is checked ray by ray on the device (cast_ray_ok).  A
+// traversed box without a camera (vrt_shade_rays) gets a settled bitmap of its own or none: the window around the camera
+// has no centre there.
 static int fill_scene_params(MarchParams& P, const vrt_scene* sc, const vrt_settings* st, const vrt_camera* cam,
                              const vrt_traversed* trav, uint64_t* d_stats) {
-    if (!sc || check_settings(st) != VRT_OK || (!cam && trav)) return VRT_ERR_ARG;
+    if (!sc || check_settings(st) != VRT_OK) return VRT_ERR_ARG;
     if (sc->chunk_size != st->chunk_size || sc->n_materials < 0 || sc->n_materials > 255) return VRT_ERR_ARG;
     if (!sc->d_chunk_table || (sc->n_slots > 0 && !sc->d_voxels) || (sc->n_materials > 0 && !sc->d_materials))
         return VRT_ERR_ARG;
@@ -4593,7 +4762,7 @@ static int fill_scene_params(MarchParams& P, const vrt_scene* sc, const vrt_sett
         const int win_env = env_int("VRT_TRAV_WINDOW", 1);  // (0: no bitmap for large boxes; 2: the window for every box of 32^3 cells and more -- tests)
         if (trav_lds && win_env != 2 && tcells <= VRT_TRAV_LDS_MAX && words * 4 <= room) {
             P.trav_words = (int32_t)words;
-        } else if (trav_lds && win_env != 0 && 32 * 32 * 32 / 8 <= room && trav->dims[0] >= 32 && trav->dims[1] >= 32 &&
+        } else if (cam && trav_lds && win_env != 0 && 32 * 32 * 32 / 8 <= room && trav->dims[0] >= 32 && trav->dims[1] >= 32 &&
                    trav->dims[2] >= 32 && trav->dims[0] < 1024 + 32 && trav->dims[1] < 1024 + 32 && trav->dims[2] < 1024 + 32) {
             // The box is sized for the rays' reach, the visits fall where the rays are: around the camera.  A bitmap over the
             // 32^3 cells centred on the camera's (4 KiB) settles nearly all of them (config 5: recording `traversed` cost 14 %
@@ -5599,7 +5768,71 @@ static void launch_cast(MarchParams P, int grid, int resmode, hipStream_t stream
     else hipLaunchKernelGGL((cast_kernel<VRT_SPEC, 2>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
 }
 
+// ---- shaded explicit rays (vrt_shade_rays) ---------------------------------------------------------------------------------
+// kernel variant: resolution mode and speculation depth as launch_cast chooses them; LDS room as launch_march does for a
+// one-ray-per-lane launch (materials | chunk table, if it fits | settled bitmap)
+template <bool RECORD>
+static void launch_shade(MarchParams P, int grid, int resmode, hipStream_t stream) {
+    P.wt_on = 0;
+    const size_t lds = march_lds(P, false, false);
+    if (resmode == 0) hipLaunchKernelGGL((shade_kernel<VRT_SPEC_DEEP, 0, RECORD>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
+    else if (resmode == 1) hipLaunchKernelGGL((shade_kernel<VRT_SPEC_DEEP, 1, RECORD>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
+    else hipLaunchKernelGGL((shade_kernel<VRT_SPEC, 2, RECORD>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
+}
+
 extern "C" {
+
+int vrt_shade_workspace_bytes(int64_t n_rays, int64_t* bytes) {
+    if (n_rays < 0 || !bytes) return VRT_ERR_ARG;
+    *bytes = 256 + align256(2 * VRT_PW_SLOTS * 8);  // the launch-wide ray counter | the frame's pow memo
+    return VRT_OK;
+}
+
+int vrt_shade_rays(const vrt_scene* scene, const vrt_settings* st, const vrt_cast_ray* d_rays, int64_t n_rays, double max_life,
+                   const double* d_draws, int32_t n_draws, void* d_workspace, int64_t workspace_bytes, uint32_t* d_rgba,
+                   vrt_ray* d_records, uint64_t* d_stats, const vrt_traversed* trav, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    MarchParams P;
+    int rc = fill_scene_params(P, scene, st, nullptr, trav, d_stats);  // (every check comes before any HIP call)
+    if (rc != VRT_OK) return rc;
+    if (n_rays < 0 || n_rays >= 4294967295ll || !(max_life > 0.0) || !(max_life <= 0x1p28)) return VRT_ERR_ARG;
+    if (n_draws < 0 || (n_draws > 0 && !d_draws) || !d_workspace) return VRT_ERR_ARG;
+    if (n_rays > 0 && !d_rgba && !d_records) return VRT_ERR_ARG;
+    if (n_rays > 0 && (!d_rays || ((uintptr_t)d_rays & 63) != 0)) return VRT_ERR_ARG;
+    int64_t need = 0;
+    vrt_shade_workspace_bytes(n_rays, &need);
+    if (workspace_bytes < need) return VRT_ERR_WORKSPACE;
+    unsigned long long* qh = (unsigned long long*)d_workspace;
+    P.pow_global = device_pow_memo(1 + st->falloff);
+    const bool frame_memo = P.pow_global == nullptr;
+    if (frame_memo) P.pow_global = (unsigned long long*)((char*)d_workspace + 256);
+    frame_begin(d_stats, qh, n_rays > 0 ? 64 : 0, P.pow_global, frame_memo && n_rays > 0 ? 4 * VRT_PW_SLOTS : 0, trav, stream);
+    const int resmode = res_mode(scene);
+    const bool big = march_big_scene(scene);
+    P.lens = max_life;  // (shade_kernel: the bound on a ray's life)
+    P.queue_head = qh;
+    P.tab.rec = reinterpret_cast<RayRecord*>(const_cast<vrt_cast_ray*>(d_rays));
+    P.draws = d_draws;
+    P.n_draws = n_draws;
+    P.draw_stride = n_draws;
+    P.first_draw = 0;
+    P.ray_rgba = d_rgba;
+    P.rays = d_records;
+    const int64_t per_launch = batch_rays();
+    for (int64_t r0 = 0; r0 < n_rays; r0 += per_launch) {
+        const int64_t n = n_rays - r0 < per_launch ? n_rays - r0 : per_launch;
+        if (r0 > 0) clear_words(qh, 8, stream);
+        P.ray0 = r0;
+        P.n = n;
+        P.chunk = march_chunk(n);
+        march_policy(big, n, P.t_hit, P.t_end, P.max_iters);
+        ProfScope ps(stream, VRT_PROF_MARCH);
+        if (d_records) launch_shade<true>(P, march_grid(n), resmode, stream);
+        else launch_shade<false>(P, march_grid(n), resmode, stream);
+    }
+    HIP_TRY(hipGetLastError());
+    return VRT_OK;
+}
 
 int vrt_cast_rays(const vrt_scene* scene, const vrt_settings* st, const vrt_cast_ray* d_rays, int64_t n_rays, double max_life,
                   vrt_hit* d_hits, uint64_t* d_stats, void* stream_) {
