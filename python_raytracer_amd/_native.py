@@ -225,6 +225,9 @@ def lib():
     # diagnostic, not part of include/vrt.h: what the calling thread's last frame-march launch kept in LDS (PLAN_* below)
     L.vrt_diag_last_plan.restype = C.c_int
     L.vrt_diag_last_plan.argtypes = [C.POINTER(i64), C.c_int]
+    # diagnostic, not part of include/vrt.h: which march instance a launch with the given inputs runs (march_variant below)
+    L.vrt_diag_march_variant.restype = C.c_int
+    L.vrt_diag_march_variant.argtypes = [C.POINTER(i32), C.c_int, C.c_char_p, C.c_int, C.POINTER(i32)]
     if L.vrt_abi_version() != ABI_VERSION:
         raise ImportError("python_raytracer_amd/_vrt.so has ABI version %d, expected %d"
                           % (L.vrt_abi_version(), ABI_VERSION))
@@ -262,6 +265,25 @@ def last_plan():
     k = len(PLAN_FIELDS) + 1
     plan["probes"] = [dict(zip(PLAN_PROBE_FIELDS, w[k + 5 * i:k + 5 * i + 5])) for i in range(w[len(PLAN_FIELDS)])]
     return plan
+
+
+VARIANT_INPUTS = ("record", "list", "list_seed", "pool", "resmode", "deep", "per_pixel", "wt_on", "keys", "trav_words", "bm_window",
+                  "big_scene", "tile_heads", "occ", "lookup", "defer_visit")
+VARIANT_DEFAULTS = {**dict.fromkeys(VARIANT_INPUTS, 0), "bm_window": -1, "defer_visit": 1}
+
+
+def march_variant(**inputs):
+    """vrt_diag_march_variant: the march instance a launch with these VARIANT_INPUTS runs (those not given: no records, no
+    list, no pool, resolution mode 0, nothing set, VRT_DEFER_VISIT unset), as (status, name, effects) -- name with every
+    template argument, effects the launch's (wt_on, trav_words, tile heads still set); name and effects are None unless status is 0.
+    Host memory only: needs no GPU."""
+    unknown = set(inputs) - set(VARIANT_INPUTS)
+    if unknown:
+        raise TypeError("unknown inputs: %s" % sorted(unknown))
+    words = (C.c_int32 * len(VARIANT_INPUTS))(*[int({**VARIANT_DEFAULTS, **inputs}[k]) for k in VARIANT_INPUTS])
+    name, effects = C.create_string_buffer(128), (C.c_int32 * 3)()
+    status = lib().vrt_diag_march_variant(words, len(VARIANT_INPUTS), name, len(name), effects)
+    return (status, name.value.decode(), tuple(effects)) if status == 0 else (status, None, None)
 
 
 def check(status, what):

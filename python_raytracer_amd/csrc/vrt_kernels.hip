@@ -25,6 +25,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <mutex>
 #include <vector>
@@ -4298,16 +4299,21 @@ __global__ void __launch_bounds__(VRT_BLOCK) frame_begin_kernel(uint32_t* stats,
     for (int i = threadIdx.x; i < n_count; i += VRT_BLOCK) count[i] = 0u;
     for (int i = threadIdx.x; i < n_pow; i += VRT_BLOCK) pow_memo[i] = 0u;
 }
-static inline void frame_begin(uint64_t* d_stats, void* count, int n_count_words, void* pow_memo, int n_pow_words, const vrt_traversed* trav,
+static inline void frame_begin(uint64_t* d_stats, void* count, int n_count_words, void* pow_memo, int n_pow_words, uint64_t* keys, int64_t n_keys,
                                hipStream_t stream) {
-    int64_t n_keys = 0;
-    if (trav && trav->d_keys && trav->reset) n_keys = (int64_t)trav->dims[0] * trav->dims[1] * trav->dims[2];  // (fill_params checked them)
     const int64_t kb = (n_keys + VRT_BLOCK * 8 - 1) / (VRT_BLOCK * 8);
     hipLaunchKernelGGL(frame_begin_kernel, dim3((unsigned)(kb < 1 ? 1 : (kb > 1024 ? 1024 : kb))), dim3(VRT_BLOCK), 0, stream, (uint32_t*)d_stats,
-                       (int)(2 * VRT_NSTATS), (uint32_t*)count, n_count_words, (uint32_t*)pow_memo, n_pow_words,
-                       n_keys ? (unsigned long long*)trav->d_keys : nullptr, n_keys);
+                       (int)(2 * VRT_NSTATS), (uint32_t*)count, n_count_words, (uint32_t*)pow_memo, n_pow_words, (unsigned long long*)keys, n_keys);
+}
+static inline void frame_begin(uint64_t* d_stats, void* count, int n_count_words, void* pow_memo, int n_pow_words, const vrt_traversed* trav,
+                               hipStream_t stream) {
+    const bool reset = trav && trav->d_keys && trav->reset;  // (fill_params checked the dimensions)
+    frame_begin(d_stats, count, n_count_words, pow_memo, n_pow_words, reset ? trav->d_keys : nullptr,
+                reset ? (int64_t)trav->dims[0] * trav->dims[1] * trav->dims[2] : 0, stream);
 }
 static inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+// the plan's seed index of every ray slot: behind the header and the list of distinct seeds
+static inline const uint32_t* plan_seedidx(const void* d_plan, int64_t slots) { return (const uint32_t*)((const char*)d_plan + 64 + align256(slots * 4)); }
 
 // march grid: persistent workgroups; each wave owns a contiguous range of the launch's rays
 static int march_grid(int64_t n) {
@@ -4353,6 +4359,12 @@ static unsigned long long* device_pow_memo(double y) {
         if (g_memos[i].dev == dev && g_memos[i].y == y) return g_memos[i].buf;
     return nullptr;
 }
+// a frame's pow memo: the device's table for its exponent, else the frame's own in its workspace, of which frame_begin clears `clear` words
+struct FrameMemo { unsigned long long* p; int clear; };
+static FrameMemo frame_memo(const vrt_settings* st, void* in_workspace, bool any_rays) {
+    unsigned long long* m = device_pow_memo(1 + st->falloff);
+    return {m ? m : (unsigned long long*)in_workspace, !m && any_rays ? 4 * VRT_PW_SLOTS : 0};
+}
 
 // rays per hand-out for a launch of n rays: 512, but 256 / 128 for small launches (about one 512-ray chunk per wave
 // would leave nothing to balance: config 2's 2 M rays march in 0.62 instead of 0.73 ms; a 1/8 share of config 3 in
@@ -4370,10 +4382,8 @@ static int march_chunk(int64_t n) {
 
 // the voxel data is far larger than L2 + Infinity Cache (config 5): most lookups miss, and the scheduling thresholds that
 // suit it differ (march_policy)
-static bool march_big_scene(const vrt_scene* sc) {
-    const int64_t bytes = (int64_t)sc->n_slots * sc->chunk_size * sc->chunk_size * sc->chunk_size;
-    return bytes > ((int64_t)512 << 20);
-}
+static inline bool big_voxels(int64_t bytes) { return bytes > ((int64_t)512 << 20); }
+static bool march_big_scene(const vrt_scene* sc) { return big_voxels((int64_t)sc->n_slots * sc->chunk_size * sc->chunk_size * sc->chunk_size); }
 // reference iterations fetched together per march pass: VRT_SPEC_DEEP (8) for scenes of resolutions 1 and 2 -- measured
 // on MI355X after the per-position cost fell to ~18 VALU instructions: config 3 6.87 ms with 8 against 7.21 (4), 7.04 (6),
 // 7.49 (12); config 5 305 ms against 392 (4), 326 (6), 316 (12) -- and for big scenes of any resolution; VRT_SPEC (4) for
@@ -4592,10 +4602,7 @@ int vrt_plan_build(const vrt_settings* st, const int32_t* d_pixels_xy, int64_t n
     h.pad = 0;
     HIP_TRY(hipMemcpyAsync(hdr, &h, sizeof h, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemsetAsync(bitmap, 0, (size_t)words * 4, stream));
-    TileGeom g;
-    g.pixels = d_pixels_xy;
-    g.n_px = n_px;
-    g.smax = smax;
+    const TileGeom g = {d_pixels_xy, n_px, smax};
     if (n_px > 0) hipLaunchKernelGGL(plan_mark_kernel, dim3(grid_for(n_px)), dim3(VRT_BLOCK), 0, stream, *st, g, bitmap, hdr);
     hipLaunchKernelGGL(plan_blocksum_kernel, dim3((unsigned)blocks), dim3(VRT_BLOCK), 0, stream, bitmap, words, block_sums);
     hipLaunchKernelGGL(plan_scan_sums_kernel, dim3(1), dim3(VRT_BLOCK), 0, stream, block_sums, blocks, hdr);
@@ -4836,13 +4843,6 @@ static int lookup_mode() {
 // (VRT_POOL and VRT_POOL_MIN_RAYS are read at every launch, not once per process: the parity tests run every case with
 // both kernels in one process)
 static bool march_pool() { return env_int("VRT_POOL", VRT_POOL_DEFAULT) != 0; }
-// Which launches without a settled bitmap run the instances that compare a traversed key after the voxel reads went out
-// (DEFER): VRT_DEFER_VISIT=1 (default) those over scenes far larger than the caches, 0 none, 2 all of them (the parity
-// tests).  Read at every launch; scheduling only, never a result.
-static bool march_defer(const MarchParams& P) {
-    const int m = env_int("VRT_DEFER_VISIT", 1);
-    return m >= 2 || (m == 1 && (int64_t)P.vox_bytes > ((int64_t)512 << 20));
-}
 // Measured optima on MI355X (tools/sweep_pool.py, same-run comparisons in profiles/r03_pool_sweep.md): config 3
 // 40 / 60 / 8 / 8 / 40 / 3 (march 5.45 ms against 6.12 ms for march_kernel), config 5 48 / 32 / 4 / 8 / 40 / 5 (263.7 against
 // 285.5 ms); VRT_POOL_T_HIT, _T_END, _SWAP_MIN, _REFILL_MIN, _KEEP, _ITERS override (scheduling only, never a result)
@@ -4972,156 +4972,176 @@ static bool pool_plan(MarchParams& P) {
     return false;
 }
 
-// kernel variant: resolution mode from vrt_scene.max_resolution, speculation depth from the scene size
-template <bool RECORD, bool LIST>
-static int launch_march(MarchParams P, int grid, int resmode, bool deep, bool pool, hipStream_t stream) {
-    if (RECORD || LIST) {  // debug records / re-traces: one generic variant
-        P.wt_on = 0;
+// ---- which kernel a march launch runs ----------------------------------------------------------------------------------
+// One instance of march_kernel (one ray per lane) or of march_pool_kernel (the ray pool), named by its template arguments
+struct MarchVariant { int pool, spec, res, record, list, lk, perpix, w, defer, tile, seed; };
+typedef void (*MarchFn)(MarchParams);
+struct MarchInstance { MarchVariant v; MarchFn fn; const char* name; };
+// Every instance the library ships, one line each: X(pool, SPEC, RESMODE, RECORD, LIST, LK, PERPIX, W, DEFER, TILE, SEED).
+// (The sixth line is the one instance no launch selects: the record / re-trace variant that neither records nor re-traces.)
+#define VRT_MARCH_INSTANCES(X) \
+    X(0, VRT_SPEC, 2, true, false, 0, 4, false, false, false, 0) \
+    X(0, VRT_SPEC, 2, false, true, 0, 4, false, false, false, 1) \
+    X(0, VRT_SPEC, 2, false, true, 0, 4, false, false, false, 2) \
+    X(0, VRT_SPEC, 2, true, true, 0, 4, false, false, false, 1) \
+    X(0, VRT_SPEC, 2, true, true, 0, 4, false, false, false, 2) \
+    X(0, VRT_SPEC, 2, false, false, 0, 4, false, false, false, 0) \
+    X(0, VRT_SPEC_DEEP, 0, false, false, 0, 0, false, false, false, 0) \
+    X(0, VRT_SPEC_DEEP, 0, false, false, 0, 2, false, false, false, 0) \
+    X(0, VRT_SPEC_DEEP, 0, false, false, 1, 0, false, false, false, 0) \
+    X(0, VRT_SPEC_DEEP, 0, false, false, 1, 2, false, false, false, 0) \
+    X(0, VRT_SPEC_DEEP, 0, false, false, 2, 0, false, false, false, 0) \
+    X(0, VRT_SPEC_DEEP, 0, false, false, 2, 2, false, false, false, 0) \
+    X(0, VRT_SPEC_DEEP, 1, false, false, 0, 0, false, false, false, 0) \
+    X(0, VRT_SPEC_DEEP, 1, false, false, 0, 2, false, false, false, 0) \
+    X(0, VRT_SPEC_DEEP, 1, false, false, 1, 0, false, false, false, 0) \
+    X(0, VRT_SPEC_DEEP, 1, false, false, 1, 2, false, false, false, 0) \
+    X(0, VRT_SPEC_DEEP, 1, false, false, 2, 0, false, false, false, 0) \
+    X(0, VRT_SPEC_DEEP, 1, false, false, 2, 2, false, false, false, 0) \
+    X(0, VRT_SPEC_DEEP, 2, false, false, 0, 0, false, false, false, 0) \
+    X(0, VRT_SPEC_DEEP, 2, false, false, 0, 2, false, false, false, 0) \
+    X(0, VRT_SPEC, 0, false, false, 0, 0, false, false, false, 0) \
+    X(0, VRT_SPEC, 0, false, false, 0, 2, false, false, false, 0) \
+    X(0, VRT_SPEC, 0, false, false, 1, 0, false, false, false, 0) \
+    X(0, VRT_SPEC, 0, false, false, 1, 2, false, false, false, 0) \
+    X(0, VRT_SPEC, 0, false, false, 2, 0, false, false, false, 0) \
+    X(0, VRT_SPEC, 0, false, false, 2, 2, false, false, false, 0) \
+    X(0, VRT_SPEC, 1, false, false, 0, 0, false, false, false, 0) \
+    X(0, VRT_SPEC, 1, false, false, 0, 2, false, false, false, 0) \
+    X(0, VRT_SPEC, 1, false, false, 1, 0, false, false, false, 0) \
+    X(0, VRT_SPEC, 1, false, false, 1, 2, false, false, false, 0) \
+    X(0, VRT_SPEC, 1, false, false, 2, 0, false, false, false, 0) \
+    X(0, VRT_SPEC, 1, false, false, 2, 2, false, false, false, 0) \
+    X(0, VRT_SPEC, 2, false, false, 0, 0, false, false, false, 0) \
+    X(0, VRT_SPEC, 2, false, false, 0, 2, false, false, false, 0) \
+    X(0, 8, 0, false, false, 0, 0, true, false, false, 0) \
+    X(0, 8, 0, false, false, 0, 2, true, false, false, 0) \
+    X(0, 8, 0, false, false, 0, 0, false, true, false, 0) \
+    X(0, 8, 0, false, false, 0, 2, false, true, false, 0) \
+    X(0, 8, 0, false, false, 0, 3, false, true, false, 0) \
+    X(0, 8, 0, false, false, 0, 3, false, false, false, 0) \
+    X(0, 8, 1, false, false, 0, 0, true, false, false, 0) \
+    X(0, 8, 1, false, false, 0, 2, true, false, false, 0) \
+    X(0, 8, 1, false, false, 0, 0, false, true, false, 0) \
+    X(0, 8, 1, false, false, 0, 2, false, true, false, 0) \
+    X(0, 8, 1, false, false, 0, 3, false, true, false, 0) \
+    X(0, 8, 1, false, false, 0, 3, false, false, false, 0) \
+    X(1, VRT_SPEC_DEEP, 0, false, false, 0, 0, false, false, false, 0) \
+    X(1, VRT_SPEC_DEEP, 0, false, false, 0, 1, false, false, false, 0) \
+    X(1, VRT_SPEC_DEEP, 1, false, false, 0, 0, false, false, false, 0) \
+    X(1, VRT_SPEC_DEEP, 1, false, false, 0, 1, false, false, false, 0) \
+    X(1, VRT_SPEC_DEEP, 2, false, false, 0, 0, false, false, false, 0) \
+    X(1, VRT_SPEC_DEEP, 2, false, false, 0, 1, false, false, false, 0) \
+    X(1, VRT_SPEC, 0, false, false, 0, 0, false, false, false, 0) \
+    X(1, VRT_SPEC, 0, false, false, 0, 1, false, false, false, 0) \
+    X(1, VRT_SPEC, 1, false, false, 0, 0, false, false, false, 0) \
+    X(1, VRT_SPEC, 1, false, false, 0, 1, false, false, false, 0) \
+    X(1, VRT_SPEC, 2, false, false, 0, 0, false, false, false, 0) \
+    X(1, VRT_SPEC, 2, false, false, 0, 1, false, false, false, 0) \
+    X(1, 8, 0, false, false, 0, 0, true, false, false, 0) \
+    X(1, 8, 0, false, false, 0, 1, true, false, false, 0) \
+    X(1, 8, 0, false, false, 0, 0, false, true, false, 0) \
+    X(1, 8, 0, false, false, 0, 1, false, true, false, 0) \
+    X(1, 8, 0, false, false, 0, 3, false, true, false, 0) \
+    X(1, 8, 0, false, false, 0, 0, false, true, true, 0) \
+    X(1, 8, 0, false, false, 0, 1, false, true, true, 0) \
+    X(1, 8, 0, false, false, 0, 3, false, false, false, 0) \
+    X(1, 8, 1, false, false, 0, 0, true, false, false, 0) \
+    X(1, 8, 1, false, false, 0, 1, true, false, false, 0) \
+    X(1, 8, 1, false, false, 0, 0, false, true, false, 0) \
+    X(1, 8, 1, false, false, 0, 1, false, true, false, 0) \
+    X(1, 8, 1, false, false, 0, 3, false, true, false, 0) \
+    X(1, 8, 1, false, false, 0, 0, false, true, true, 0) \
+    X(1, 8, 1, false, false, 0, 1, false, true, true, 0) \
+    X(1, 8, 1, false, false, 0, 3, false, false, false, 0)
+#define VRT_FN_0(S, R, REC, LI, LK, PP, W, D, T, SD) march_kernel<S,R,REC,LI,LK,PP,W,D,SD>
+#define VRT_FN_1(S, R, REC, LI, LK, PP, W, D, T, SD) march_pool_kernel<S,R,PP,W,D,T>
+#define VRT_STR_(...) #__VA_ARGS__
+#define VRT_STR(...) VRT_STR_(__VA_ARGS__)
+#define VRT_ROW(POOL, ...) {{POOL, __VA_ARGS__}, &VRT_FN_##POOL(__VA_ARGS__), VRT_STR(VRT_FN_##POOL(__VA_ARGS__))},
+static const MarchInstance g_march_instances[] = {VRT_MARCH_INSTANCES(VRT_ROW)};
+#undef VRT_ROW
+
+// the 8-position kernels of the byte lookup -- look-ahead (W), late key comparison (DEFER), no ray table (PERPIX 3) -- exist
+// for this launch: resolutions <= 2, the deep speculation compiled as 8 positions
+static inline bool march_eight(int resmode, bool deep, int lookup) { return deep && VRT_SPEC_DEEP == 8 && resmode != 2 && lookup == 0; }
+
+// What march_choose decides from: plain values, so the policy can be asked without a GPU (vrt_diag_march_variant, which takes
+// them as int32 words in this order).  keys / tile_heads / occ: the launch has traversed keys / tile heads / an occupancy
+// table; big_scene: march_big_scene; lookup: lookup_mode(); defer_visit: VRT_DEFER_VISIT.
+struct MarchChoiceIn {
+    int32_t record, list, list_seed, pool, resmode, deep, per_pixel, wt_on, keys, trav_words, bm_window, big_scene, tile_heads, occ, lookup,
+        defer_visit;
+};
+// ... and what it decides: the instance, and what the choice does to the launch's parameters
+struct MarchChoice {
+    const MarchInstance* k;
+    int32_t wt_on, trav_words, keep_tile_heads;
+};
+// Pure: reads no environment variable, makes no HIP call, touches no global.  VRT_ERR_ARG: no kernel exists for the combination.
+static int march_choose(const MarchChoiceIn& in, MarchChoice& c) {
+    MarchVariant v = {in.pool != 0, VRT_SPEC, 2, in.record != 0, in.list != 0, 0, 4, 0, 0, 0, in.list ? in.list_seed : 0};
+    c = {nullptr, in.wt_on, in.trav_words, 1};
+    if (in.record || in.list) {  // debug records / re-traces: one generic variant, one ray per lane
+        c.wt_on = 0;
         // A re-trace launch hands its rays out in the order the frame's march appended them to the list, not in increasing
         // ray order: the smallest index a wave holds says nothing about the rays it will still take, so no cell may be
         // called settled (see trav_cell) -- every visit compares its key with the cell's.
-        if (LIST) P.trav_words = 0;
-        const size_t lds = march_lds(P, false, false);
-        if (!LIST) plan_record(P, lds, false);
-        if (LIST && P.list_seed == 1)
-            hipLaunchKernelGGL((march_kernel<VRT_SPEC, 2, RECORD, LIST, 0, 4, false, false, LIST ? 1 : 0>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
-        else if (LIST && P.list_seed == 2)
-            hipLaunchKernelGGL((march_kernel<VRT_SPEC, 2, RECORD, LIST, 0, 4, false, false, LIST ? 2 : 0>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
-        else
-            hipLaunchKernelGGL((march_kernel<VRT_SPEC, 2, RECORD, LIST>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
-        return VRT_OK;
-    }
-    if (pool) {
-        pool_policy(P, (int64_t)P.vox_bytes > ((int64_t)512 << 20));
-        const size_t lds = march_lds(P, false, true);
-        plan_record(P, lds, true);
-#define VRT_LAUNCH_POOL_W(SPEC_, RES_, W_)                                                                                 \
-    do {                                                                                                                   \
-        if (P.per_pixel)                                                                                                   \
-            hipLaunchKernelGGL((march_pool_kernel<SPEC_, RES_, 1, W_>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);       \
-        else                                                                                                               \
-            hipLaunchKernelGGL((march_pool_kernel<SPEC_, RES_, 0, W_>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);       \
-    } while (0)
-#define VRT_LAUNCH_POOL(SPEC_, RES_) VRT_LAUNCH_POOL_W(SPEC_, RES_, false)
-        // no settled bitmap, but keys to record (config 5: the box is too large for one): the DEFER instances (8 positions,
-        // resolutions <= 2)
-        // -- for scenes far larger than the caches only, where a step's voxel reads are misses worth overlapping with: config 5
-        // 233.8 against 244.3 ms; config 3, whose pools leave the bitmap no room either, 5.39 against 5.33 ms with it
-        // (a bitmap over the cells around the camera only -- boxes too large for their own -- goes with them)
-        const bool defer = !P.wt_on && deep && VRT_SPEC_DEEP == 8 && resmode != 2 && P.t_keys && (P.trav_words == 0 || P.bm_window >= 0) && march_defer(P);
-        // (the tiled hand-out: instances of the DEFER kernels with a ray table)
-        if (!defer || P.per_pixel == 2) P.tile_heads = nullptr;
-        if (P.per_pixel == 2) {  // no ray table (take_ray, PERPIX 3): vrt_render_tile asks for this with 8 positions only
-            if (P.wt_on || !deep || VRT_SPEC_DEEP != 8 || resmode == 2) return VRT_ERR_ARG;
-            if (defer && resmode == 0) hipLaunchKernelGGL((march_pool_kernel<8, 0, 3, false, true>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
-            else if (defer) hipLaunchKernelGGL((march_pool_kernel<8, 1, 3, false, true>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
-            else if (resmode == 0) hipLaunchKernelGGL((march_pool_kernel<8, 0, 3>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
-            else hipLaunchKernelGGL((march_pool_kernel<8, 1, 3>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
-        } else if (P.wt_on) {  // (only with 8 positions and resolutions <= 2: march_wt_ok)
-            if (resmode == 0) VRT_LAUNCH_POOL_W(8, 0, true);
-            else VRT_LAUNCH_POOL_W(8, 1, true);
-        } else if (defer) {
-#define VRT_LAUNCH_POOL_D(RES_)                                                                                                    \
-    do {                                                                                                                         \
-        if (P.tile_heads && P.per_pixel)                                                                                         \
-            hipLaunchKernelGGL((march_pool_kernel<8, RES_, 1, false, true, true>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);   \
-        else if (P.tile_heads)                                                                                                   \
-            hipLaunchKernelGGL((march_pool_kernel<8, RES_, 0, false, true, true>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);   \
-        else if (P.per_pixel)                                                                                                    \
-            hipLaunchKernelGGL((march_pool_kernel<8, RES_, 1, false, true>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);         \
-        else                                                                                                                     \
-            hipLaunchKernelGGL((march_pool_kernel<8, RES_, 0, false, true>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);         \
-    } while (0)
-            if (resmode == 0) VRT_LAUNCH_POOL_D(0);
-            else VRT_LAUNCH_POOL_D(1);
-#undef VRT_LAUNCH_POOL_D
-        } else if (deep) {
-            if (resmode == 0) VRT_LAUNCH_POOL(VRT_SPEC_DEEP, 0);
-            else if (resmode == 1) VRT_LAUNCH_POOL(VRT_SPEC_DEEP, 1);
-            else VRT_LAUNCH_POOL(VRT_SPEC_DEEP, 2);
-        } else {
-            if (resmode == 0) VRT_LAUNCH_POOL(VRT_SPEC, 0);
-            else if (resmode == 1) VRT_LAUNCH_POOL(VRT_SPEC, 1);
-            else VRT_LAUNCH_POOL(VRT_SPEC, 2);
-        }
-#undef VRT_LAUNCH_POOL
-#undef VRT_LAUNCH_POOL_W
-        return VRT_OK;
-    }
-    const int lk = lookup_mode();
-    if (lk != 0 && (!P.occ || resmode == 2)) return VRT_ERR_ARG;  // the measurement variants exist for resolutions <= 2
-    // One ray per lane: where the key comparison can go behind the voxel reads (the DEFER instances) a bitmap over the cells
-    // around the camera only is not worth its upkeep -- config 5 261.8 against 254.4 ms (the ray pool: 232.1 against 233.7)
-    if (P.bm_window >= 0 && !P.wt_on && lk == 0 && deep && VRT_SPEC_DEEP == 8 && resmode != 2 && P.t_keys && march_defer(P))
-        P.trav_words = 0;  // (march_kernel's DEFER instances have no code for one)
-    const size_t lds = march_lds(P, lk == 2, false);
-    plan_record(P, lds, false);
-    if (P.wt_on) {  // (only with 8 positions, resolutions <= 2 and the byte lookup: march_wt_ok)
-#define VRT_LAUNCH_W(RES_)                                                                                                          \
-    do {                                                                                                                            \
-        if (P.per_pixel)                                                                                                            \
-            hipLaunchKernelGGL((march_kernel<8, RES_, false, false, 0, 2, true>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);       \
-        else                                                                                                                        \
-            hipLaunchKernelGGL((march_kernel<8, RES_, false, false, 0, 0, true>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);       \
-    } while (0)
-        if (resmode == 0) VRT_LAUNCH_W(0);
-        else VRT_LAUNCH_W(1);
-#undef VRT_LAUNCH_W
-        return VRT_OK;
-    }
-    if (P.per_pixel == 2) {  // no ray table (take_ray, PERPIX 3): vrt_render_tile asks for this with 8 positions only
-        if (lk != 0 || !deep || VRT_SPEC_DEEP != 8 || resmode == 2) return VRT_ERR_ARG;
-        const bool defer = P.t_keys && (P.trav_words == 0 || P.bm_window >= 0) && march_defer(P);
-        if (defer && resmode == 0) hipLaunchKernelGGL((march_kernel<8, 0, false, false, 0, 3, false, true>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
-        else if (defer) hipLaunchKernelGGL((march_kernel<8, 1, false, false, 0, 3, false, true>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
-        else if (resmode == 0) hipLaunchKernelGGL((march_kernel<8, 0, false, false, 0, 3>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
-        else hipLaunchKernelGGL((march_kernel<8, 1, false, false, 0, 3>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
-        return VRT_OK;
-    }
-    if (lk == 0 && deep && VRT_SPEC_DEEP == 8 && resmode != 2 && P.t_keys && (P.trav_words == 0 || P.bm_window >= 0) && march_defer(P)) {  // (see the pool's)
-#define VRT_LAUNCH_D(RES_)                                                                                                                \
-    do {                                                                                                                                  \
-        if (P.per_pixel)                                                                                                                  \
-            hipLaunchKernelGGL((march_kernel<8, RES_, false, false, 0, 2, false, true>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);      \
-        else                                                                                                                              \
-            hipLaunchKernelGGL((march_kernel<8, RES_, false, false, 0, 0, false, true>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);      \
-    } while (0)
-        if (resmode == 0) VRT_LAUNCH_D(0);
-        else VRT_LAUNCH_D(1);
-#undef VRT_LAUNCH_D
-        return VRT_OK;
-    }
-#define VRT_LAUNCH(SPEC_, RES_, LK_)                                                                                        \
-    do {                                                                                                                    \
-        if (P.per_pixel)                                                                                                    \
-            hipLaunchKernelGGL((march_kernel<SPEC_, RES_, false, false, LK_, 2>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P); \
-        else                                                                                                                \
-            hipLaunchKernelGGL((march_kernel<SPEC_, RES_, false, false, LK_, 0>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P); \
-    } while (0)
-#define VRT_LAUNCH_LK(SPEC_, RES_)                \
-    do {                                          \
-        if (lk == 0) VRT_LAUNCH(SPEC_, RES_, 0);  \
-        else if (lk == 1) VRT_LAUNCH(SPEC_, RES_, 1); \
-        else VRT_LAUNCH(SPEC_, RES_, 2);          \
-    } while (0)
-    if (deep) {
-        if (resmode == 0) VRT_LAUNCH_LK(VRT_SPEC_DEEP, 0);
-        else if (resmode == 1) VRT_LAUNCH_LK(VRT_SPEC_DEEP, 1);
-        else VRT_LAUNCH(VRT_SPEC_DEEP, 2, 0);
+        if (in.list) c.trav_words = 0;
     } else {
-        if (resmode == 0) VRT_LAUNCH_LK(VRT_SPEC, 0);
-        else if (resmode == 1) VRT_LAUNCH_LK(VRT_SPEC, 1);
-        else VRT_LAUNCH(VRT_SPEC, 2, 0);
+        // the measurement variants of the lookup exist for one ray per lane and resolutions <= 2
+        if (in.lookup != 0 && (in.pool || !in.occ || in.resmode == 2)) return VRT_ERR_ARG;
+        const bool eight = march_eight(in.resmode, in.deep != 0, in.lookup);
+        // no look-ahead and no march without a ray table (take_ray, PERPIX 3) but with 8 positions, and not both at once
+        // (march_wt_ok; vrt_render_tile asks for PERPIX 3 with 8 positions only)
+        if ((in.wt_on || in.per_pixel == 2) && (!eight || (in.wt_on && in.per_pixel == 2))) return VRT_ERR_ARG;
+        // No settled bitmap, but keys to record (config 5: the box is too large for one): the DEFER instances, which compare
+        // a traversed key after the voxel reads went out -- VRT_DEFER_VISIT=1 (default) for scenes far larger than the caches
+        // only, where a step's voxel reads are misses worth overlapping with: config 5 233.8 against 244.3 ms; config 3, whose
+        // pools leave the bitmap no room either, 5.39 against 5.33 ms with it; 0 never, 2 always (the parity tests).
+        // Scheduling only, never a result.  (A bitmap over the cells around the camera only -- boxes too large for their
+        // own -- goes with them.)
+        const bool defer = !in.wt_on && eight && in.keys && (in.trav_words == 0 || in.bm_window >= 0) &&
+                           (in.defer_visit >= 2 || (in.defer_visit == 1 && in.big_scene));
+        // (the tiled hand-out: instances of the pool's DEFER kernels with a ray table)
+        if (in.pool) c.keep_tile_heads = defer && in.per_pixel != 2;
+        // One ray per lane: where the key comparison can go behind the voxel reads a bitmap over the cells around the camera
+        // only is not worth its upkeep -- config 5 261.8 against 254.4 ms (the ray pool: 232.1 against 233.7) -- and
+        // march_kernel's DEFER instances have no code for one
+        else if (defer && in.bm_window >= 0) c.trav_words = 0;
+        v = {in.pool != 0, in.deep ? VRT_SPEC_DEEP : VRT_SPEC, in.resmode, 0, 0, in.lookup, in.per_pixel == 2 ? 3 : (in.per_pixel ? (in.pool ? 1 : 2) : 0),
+             in.wt_on != 0, defer, in.pool && c.keep_tile_heads && in.tile_heads, 0};
     }
-#undef VRT_LAUNCH_LK
-#undef VRT_LAUNCH
+    for (const MarchInstance& m : g_march_instances)
+        if (!c.k && memcmp(&m.v, &v, sizeof v) == 0) c.k = &m;
+    return c.k ? VRT_OK : VRT_ERR_ARG;  // (not in the table: a record launch with the pool, a re-trace whose list_seed is neither 1 nor 2: set_tier)
+}
+
+static inline void launch_fn(MarchFn fn, int grid, size_t lds, hipStream_t stream, const MarchParams& P) {
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
+}
+// the kernels that come as three instances (batched views, first hit, explicit rays): VRT_SPEC_DEEP positions per step for
+// resolutions <= 2, VRT_SPEC for the generic instance, like the frame's march of scenes that fit the caches; K(SPEC, RESMODE): the instance
+#define VRT_BY_RES(resmode, K) ((resmode) == 0 ? (MarchFn)K(VRT_SPEC_DEEP, 0) : (resmode) == 1 ? (MarchFn)K(VRT_SPEC_DEEP, 1) : (MarchFn)K(VRT_SPEC, 2))
+// kernel variant: resolution mode from vrt_scene.max_resolution, speculation depth from the scene size (march_choose)
+static int launch_march(MarchParams P, int grid, int resmode, bool deep, bool pool, bool record, bool list, hipStream_t stream) {
+    const bool big_scene = big_voxels(P.vox_bytes);
+    const MarchChoiceIn in = {record, list, P.list_seed, pool, resmode, deep, P.per_pixel, P.wt_on, P.t_keys != nullptr, P.trav_words, P.bm_window,
+                              big_scene, P.tile_heads != nullptr, P.occ != nullptr, lookup_mode(), env_int("VRT_DEFER_VISIT", 1)};
+    MarchChoice c;
+    if (march_choose(in, c) != VRT_OK) return VRT_ERR_ARG;
+    P.wt_on = c.wt_on;
+    P.trav_words = c.trav_words;
+    if (!c.keep_tile_heads) P.tile_heads = nullptr;
+    if (pool) pool_policy(P, big_scene);
+    const size_t lds = march_lds(P, c.k->v.lk == 2, pool);
+    if (!list) plan_record(P, lds, pool);
+    launch_fn(c.k->fn, grid, lds, stream, P);
     return VRT_OK;
 }
 // may this frame's march look ahead across chunk borders (march_step_w)?  fill_params has checked the scene's layout and
 // size; the kernel exists for 8 positions, resolutions <= 2 and the byte lookup
-static inline bool march_wt_ok(const MarchParams& P, int resmode, bool deep) {
-    return P.wt_on && resmode != 2 && deep && VRT_SPEC_DEEP == 8 && lookup_mode() == 0;
-}
+static inline bool march_wt_ok(const MarchParams& P, int resmode, bool deep) { return P.wt_on && march_eight(resmode, deep, lookup_mode()); }
 static inline int res_mode(const vrt_scene* sc) {
     static int force = -2;
     if (force == -2) force = env_int("VRT_RESMODE", -1);
@@ -5267,19 +5287,14 @@ static inline size_t views_lds(MarchParams& P, int64_t n_views) {  // n_views: t
     return n + (size_t)fit * VRT_VIEW_WORDS * 8;
 }
 // the frame's march of a batch (LIST false) and its two re-trace tiers (P.list_seed 1 | 2)
-template <bool LIST>
-static void launch_march_views(MarchParams P, int grid, int resmode, int64_t n_views, hipStream_t stream) {
+static void launch_march_views(MarchParams P, int grid, int resmode, bool list, int64_t n_views, hipStream_t stream) {
     const size_t lds = views_lds(P, n_views);
-    if (LIST) {  // one generic variant, like march_kernel's re-traces
-        if (P.list_seed == 1) hipLaunchKernelGGL((march_views_kernel<VRT_SPEC, 2, LIST, LIST ? 1 : 0>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
-        else hipLaunchKernelGGL((march_views_kernel<VRT_SPEC, 2, LIST, LIST ? 2 : 0>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
-    } else if (resmode == 0) {
-        hipLaunchKernelGGL((march_views_kernel<VRT_SPEC_DEEP, 0, false>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
-    } else if (resmode == 1) {
-        hipLaunchKernelGGL((march_views_kernel<VRT_SPEC_DEEP, 1, false>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
-    } else {
-        hipLaunchKernelGGL((march_views_kernel<VRT_SPEC, 2, false>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
-    }
+#define VRT_VIEWS(S, R) &march_views_kernel<S, R, false>
+    MarchFn fn = VRT_BY_RES(resmode, VRT_VIEWS);
+#undef VRT_VIEWS
+    if (list)  // one generic variant, like march_kernel's re-traces
+        fn = P.list_seed == 1 ? &march_views_kernel<VRT_SPEC, 2, true, 1> : &march_views_kernel<VRT_SPEC, 2, true, 2>;
+    launch_fn(fn, grid, lds, stream, P);
 }
 
 extern "C" {
@@ -5316,10 +5331,7 @@ int vrt_draw_table_build(const vrt_settings* st, const int32_t* d_pixels_xy, int
     int64_t need = 0;
     if (n_distinct < 0 || vrt_draw_table_bytes(n_distinct, fast_draws, &need) != VRT_OK) return VRT_ERR_ARG;
     if (table_bytes < need) return VRT_ERR_WORKSPACE;
-    TileGeom g;
-    g.pixels = d_pixels_xy;
-    g.n_px = n_px;
-    g.smax = vrt_max_samples(st);
+    const TileGeom g = {d_pixels_xy, n_px, vrt_max_samples(st)};
     ProfScope ps(stream, VRT_PROF_RNG);
     int rc = seed_draw_table(st, g, d_plan, n_distinct, fast_draws, d_table, stream);
     if (rc != VRT_OK) return rc;
@@ -5347,11 +5359,8 @@ int vrt_ray_table_build(const vrt_settings* st, double lens, const int32_t* d_pi
     const int64_t rays = n_px * smax;
     if (rays == 0) return VRT_OK;
     if (rays >= 4294967295ll) return VRT_ERR_ARG;
-    TileGeom g;
-    g.pixels = d_pixels_xy;
-    g.n_px = n_px;
-    g.smax = smax;
-    const uint32_t* ray_seedidx = (const uint32_t*)((const char*)d_plan + 64 + align256(rays * 4));
+    const TileGeom g = {d_pixels_xy, n_px, smax};
+    const uint32_t* ray_seedidx = plan_seedidx(d_plan, rays);
     ProfScope ps(stream, VRT_PROF_RAYGEN);
     const int per_pixel = ray_table_per_pixel(*st) ? 1 : 0;
     hipLaunchKernelGGL(raygen_tile_kernel, dim3(grid_for(per_pixel ? n_px : rays)), dim3(VRT_BLOCK), 0, stream, *st, lens, g,
@@ -5377,8 +5386,7 @@ int vrt_render_tile(const vrt_scene* scene, const vrt_settings* st, const vrt_ca
     if (rays >= 4294967295ll) return VRT_ERR_ARG;
     // the plan header (n_distinct, settings hash) is read back and validated by the caller once, after
     // vrt_plan_build; no host synchronisation happens here
-    const char* pl = (const char*)d_plan;
-    const uint32_t* ray_seedidx = (const uint32_t*)(pl + 64 + align256(rays * 4));
+    const uint32_t* ray_seedidx = plan_seedidx(d_plan, rays);
     if (n_distinct < 0 || n_distinct > rays || !fast_draws_ok(fast_draws)) return VRT_ERR_ARG;
     if (st->seed_nonce && n_distinct != rays) return VRT_ERR_ARG;  // non-static: one row per ray slot
     WsLayout w = ws_layout(st, n_px, n_distinct, fast_draws,
@@ -5390,15 +5398,10 @@ int vrt_render_tile(const vrt_scene* scene, const vrt_settings* st, const vrt_ca
     uint32_t* rgba = d_ray_rgba ? d_ray_rgba : (uint32_t*)(ws + w.off_rgba);
     uint32_t* list = (uint32_t*)(ws + w.off_list);
     uint32_t* count = (uint32_t*)(ws + w.off_count);
-    unsigned long long* pow_global = device_pow_memo(1 + st->falloff);
-    const bool frame_memo = pow_global == nullptr;
-    if (frame_memo) pow_global = (unsigned long long*)(ws + w.off_pow);
-    frame_begin(d_stats, count, n_px > 0 ? 64 + 8 * 32 : 0, pow_global, frame_memo && n_px > 0 ? 4 * VRT_PW_SLOTS : 0, trav, stream);
+    const FrameMemo memo = frame_memo(st, ws + w.off_pow, n_px > 0);
+    frame_begin(d_stats, count, n_px > 0 ? 64 + 8 * 32 : 0, memo.p, memo.clear, trav, stream);
     if (n_px == 0) return VRT_OK;
-    TileGeom g;
-    g.pixels = d_pixels_xy;
-    g.n_px = n_px;
-    g.smax = smax;
+    const TileGeom g = {d_pixels_xy, n_px, smax};
     if (!d_draw_table) {  // no table from vrt_draw_table_build: seed this frame's draws into the workspace
         ProfScope ps(stream, VRT_PROF_RNG);
         rc = seed_draw_table(st, g, d_plan, n_distinct, fast_draws, (double*)(ws + w.off_table), stream);
@@ -5412,8 +5415,7 @@ int vrt_render_tile(const vrt_scene* scene, const vrt_settings* st, const vrt_ca
     // A ray table that would be written now and read once is not written at all: the lanes of the march derive their
     // records from the draw rows (take_ray, PERPIX 3).  One record per pixel is cheap enough to keep its kernel; the
     // variants without a PERPIX 3 instance keep it too.  (VRT_FUSE_RAYGEN=0: always the kernel -- for measurements)
-    if (!d_ray_table && !per_pixel && !d_rays && !P.wt_on && deep && VRT_SPEC_DEEP == 8 && resmode != 2 && lookup_mode() == 0 &&
-        env_int("VRT_FUSE_RAYGEN", 1) != 0)
+    if (!d_ray_table && !per_pixel && !d_rays && !P.wt_on && march_eight(resmode, deep, lookup_mode()) && env_int("VRT_FUSE_RAYGEN", 1) != 0)
         per_pixel = 2;
     if (!d_ray_table && per_pixel != 2) {  // no table from vrt_ray_table_build: lens quaternions + lives of this frame
         ProfScope ps(stream, VRT_PROF_RAYGEN);
@@ -5424,7 +5426,7 @@ int vrt_render_tile(const vrt_scene* scene, const vrt_settings* st, const vrt_ca
     P.ray_seedidx = st->seed_nonce ? nullptr : ray_seedidx;
     P.ray_rgba = rgba;
     P.rays = d_rays;
-    P.pow_global = pow_global;
+    P.pow_global = memo.p;
     P.first_draw = 1 + (st->dof != 0.0 ? 2 : 0);
     P.per_pixel = per_pixel;
     P.lens = cam->lens;
@@ -5466,20 +5468,17 @@ int vrt_render_tile(const vrt_scene* scene, const vrt_settings* st, const vrt_ca
         }
         {
             ProfScope ps(stream, VRT_PROF_MARCH);
-            rc = d_rays ? launch_march<true, false>(F, march_grid(n), resmode, deep, false, stream)
-                        : launch_march<false, false>(F, march_grid(n), resmode, deep, pool, stream);
+            rc = launch_march(F, march_grid(n), resmode, deep, pool, d_rays != nullptr, false, stream);
             if (rc != VRT_OK) return rc;
         }
         // the re-trace tiers (set_tier): rays that ran out of draws, then those that outrun even D_SLOW draws
         ProfScope ps(stream, VRT_PROF_RETRACE);
         set_tier(P, tiers, 1);
         P.prefix_draws = pool ? fast_draws : 0;  // (see hit_body)
-        if (d_rays) launch_march<true, true>(P, 256, resmode, deep, false, stream);
-        else launch_march<false, true>(P, 256, resmode, deep, false, stream);
+        launch_march(P, 256, resmode, deep, false, d_rays != nullptr, true, stream);
         P.prefix_draws = 0;
         set_tier(P, tiers, 2);
-        if (d_rays) launch_march<true, true>(P, 64, resmode, deep, false, stream);
-        else launch_march<false, true>(P, 64, resmode, deep, false, stream);
+        launch_march(P, 64, resmode, deep, false, d_rays != nullptr, true, stream);
     }
     if (d_rgba_f32 || d_image_u8) {
         ProfScope ps(stream, VRT_PROF_RESOLVE);
@@ -5552,29 +5551,19 @@ int vrt_render_views(const vrt_scene* scene, const vrt_settings* st, const vrt_c
     uint32_t* list = (uint32_t*)(ws + w.off_list);
     uint32_t* count = (uint32_t*)(ws + w.off_count);
     double* view_tab = (double*)(ws + w.off_views);
-    unsigned long long* pow_global = device_pow_memo(1 + st->falloff);
-    const bool frame_memo = pow_global == nullptr;
-    if (frame_memo) pow_global = (unsigned long long*)(ws + w.off_pow);
-    {   // what frame_begin clears, with the keys of every view
-        const int64_t n_keys = keys && traversed[0].reset ? tcells * n_views : 0;
-        const int64_t kb = (n_keys + VRT_BLOCK * 8 - 1) / (VRT_BLOCK * 8);
-        hipLaunchKernelGGL(frame_begin_kernel, dim3((unsigned)(kb < 1 ? 1 : (kb > 1024 ? 1024 : kb))), dim3(VRT_BLOCK), 0, stream, (uint32_t*)d_stats,
-                           (int)(2 * VRT_NSTATS), count, n_px > 0 ? 64 + 8 * 32 : 0, (uint32_t*)pow_global, frame_memo && n_px > 0 ? 4 * VRT_PW_SLOTS : 0,
-                           (unsigned long long*)keys, n_keys);
-    }
+    const FrameMemo memo = frame_memo(st, ws + w.off_pow, n_px > 0);
+    frame_begin(d_stats, count, n_px > 0 ? 64 + 8 * 32 : 0, memo.p, memo.clear, keys,
+                keys && traversed[0].reset ? tcells * n_views : 0, stream);  // (the keys of every view)
     if (n_px == 0) return VRT_OK;
     setup_views(d_cams, keys ? traversed : nullptr, n_views, st->chunk_size, view_tab, stream);
-    TileGeom g;
-    g.pixels = d_pixels_xy;
-    g.n_px = n_px;
-    g.smax = smax;
+    const TileGeom g = {d_pixels_xy, n_px, smax};
     const int resmode = res_mode(scene);
     const bool big_scene = march_big_scene(scene);
     P.g = g;
-    P.ray_seedidx = (const uint32_t*)((const char*)d_plan + 64 + align256(slots * 4));
+    P.ray_seedidx = plan_seedidx(d_plan, slots);
     P.ray_rgba = rgba;
     P.rays = nullptr;
-    P.pow_global = pow_global;
+    P.pow_global = memo.p;
     P.first_draw = 1 + (st->dof != 0.0 ? 2 : 0);
     P.per_pixel = ray_table_per_pixel(*st) ? 1 : 0;
     P.lens = 0.0;
@@ -5597,14 +5586,14 @@ int vrt_render_views(const vrt_scene* scene, const vrt_settings* st, const vrt_c
         set_tier(P, tiers, 0);
         {
             ProfScope ps(stream, VRT_PROF_MARCH);
-            launch_march_views<false>(P, march_grid(n), resmode, nv, stream);
+            launch_march_views(P, march_grid(n), resmode, false, nv, stream);
         }
         // the two re-trace tiers of vrt_render_tile; their lists hold offsets in this launch, the view follows from them
         ProfScope ps(stream, VRT_PROF_RETRACE);
         set_tier(P, tiers, 1);
-        launch_march_views<true>(P, 256, resmode, nv, stream);
+        launch_march_views(P, 256, resmode, true, nv, stream);
         set_tier(P, tiers, 2);
-        launch_march_views<true>(P, 64, resmode, nv, stream);
+        launch_march_views(P, 64, resmode, true, nv, stream);
     }
     if (d_rgba_f32 || d_image_u8) {
         ProfScope ps(stream, VRT_PROF_RESOLVE);
@@ -5635,17 +5624,9 @@ static inline size_t first_hit_lds(MarchParams& P, int64_t n_views) {
 template <bool VIEWS>
 static void launch_first_hit(MarchParams P, int grid, int resmode, int64_t n_views, hipStream_t stream) {
     const size_t lds = first_hit_lds(P, VIEWS ? n_views : 0);
-#define VRT_LAUNCH_FH(SPEC_, RES_)                                                                                           \
-    do {                                                                                                                     \
-        if (P.per_pixel)                                                                                                     \
-            hipLaunchKernelGGL((first_hit_kernel<SPEC_, RES_, 1, VIEWS>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);        \
-        else                                                                                                                 \
-            hipLaunchKernelGGL((first_hit_kernel<SPEC_, RES_, 0, VIEWS>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);        \
-    } while (0)
-    if (resmode == 0) VRT_LAUNCH_FH(VRT_SPEC_DEEP, 0);
-    else if (resmode == 1) VRT_LAUNCH_FH(VRT_SPEC_DEEP, 1);
-    else VRT_LAUNCH_FH(VRT_SPEC, 2);
-#undef VRT_LAUNCH_FH
+#define VRT_FIRST_HIT(S, R) (P.per_pixel ? &first_hit_kernel<S, R, 1, VIEWS> : &first_hit_kernel<S, R, 0, VIEWS>)
+    launch_fn(VRT_BY_RES(resmode, VRT_FIRST_HIT), grid, lds, stream, P);
+#undef VRT_FIRST_HIT
 }
 // what both entry points check and set after fill_params: the pass reads no plan, draw table, materials or keys
 static int first_hit_params(MarchParams& P, const vrt_settings* st, const int32_t* d_pixels_xy, int64_t n_px, const void* d_plan,
@@ -5763,9 +5744,9 @@ int vrt_first_hit_views(const vrt_scene* scene, const vrt_settings* st, const vr
 // kernel variant: as launch_first_hit chooses it (resolution mode from vrt_scene.max_resolution)
 static void launch_cast(MarchParams P, int grid, int resmode, hipStream_t stream) {
     const size_t lds = first_hit_lds(P, 0);  // the chunk table, if it fits
-    if (resmode == 0) hipLaunchKernelGGL((cast_kernel<VRT_SPEC_DEEP, 0>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
-    else if (resmode == 1) hipLaunchKernelGGL((cast_kernel<VRT_SPEC_DEEP, 1>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
-    else hipLaunchKernelGGL((cast_kernel<VRT_SPEC, 2>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
+#define VRT_CAST(S, R) &cast_kernel<S, R>
+    launch_fn(VRT_BY_RES(resmode, VRT_CAST), grid, lds, stream, P);
+#undef VRT_CAST
 }
 
 // ---- shaded explicit rays (vrt_shade_rays) ---------------------------------------------------------------------------------
@@ -5775,9 +5756,9 @@ template <bool RECORD>
 static void launch_shade(MarchParams P, int grid, int resmode, hipStream_t stream) {
     P.wt_on = 0;
     const size_t lds = march_lds(P, false, false);
-    if (resmode == 0) hipLaunchKernelGGL((shade_kernel<VRT_SPEC_DEEP, 0, RECORD>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
-    else if (resmode == 1) hipLaunchKernelGGL((shade_kernel<VRT_SPEC_DEEP, 1, RECORD>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
-    else hipLaunchKernelGGL((shade_kernel<VRT_SPEC, 2, RECORD>), dim3(grid), dim3(VRT_BLOCK), lds, stream, P);
+#define VRT_SHADE(S, R) &shade_kernel<S, R, RECORD>
+    launch_fn(VRT_BY_RES(resmode, VRT_SHADE), grid, lds, stream, P);
+#undef VRT_SHADE
 }
 
 extern "C" {
@@ -5803,10 +5784,9 @@ int vrt_shade_rays(const vrt_scene* scene, const vrt_settings* st, const vrt_cas
     vrt_shade_workspace_bytes(n_rays, &need);
     if (workspace_bytes < need) return VRT_ERR_WORKSPACE;
     unsigned long long* qh = (unsigned long long*)d_workspace;
-    P.pow_global = device_pow_memo(1 + st->falloff);
-    const bool frame_memo = P.pow_global == nullptr;
-    if (frame_memo) P.pow_global = (unsigned long long*)((char*)d_workspace + 256);
-    frame_begin(d_stats, qh, n_rays > 0 ? 64 : 0, P.pow_global, frame_memo && n_rays > 0 ? 4 * VRT_PW_SLOTS : 0, trav, stream);
+    const FrameMemo memo = frame_memo(st, (char*)d_workspace + 256, n_rays > 0);
+    P.pow_global = memo.p;
+    frame_begin(d_stats, qh, n_rays > 0 ? 64 : 0, memo.p, memo.clear, trav, stream);
     const int resmode = res_mode(scene);
     const bool big = march_big_scene(scene);
     P.lens = max_life;  // (shade_kernel: the bound on a ray's life)
@@ -5887,10 +5867,9 @@ int vrt_trace_rays(const vrt_scene* scene, const vrt_settings* st, const vrt_cam
     if (workspace_bytes < need) return VRT_ERR_WORKSPACE;
     char* tail = (char*)d_workspace + align256(n_rays * 8 * VRT_RAY_WORDS);
     unsigned long long* qh = (unsigned long long*)tail;
-    P.pow_global = device_pow_memo(1 + st->falloff);
-    const bool frame_memo = P.pow_global == nullptr;
-    if (frame_memo) P.pow_global = (unsigned long long*)(tail + 256);
-    frame_begin(d_stats, qh, n_rays > 0 ? 64 : 0, P.pow_global, frame_memo && n_rays > 0 ? 4 * VRT_PW_SLOTS : 0, trav, stream);
+    const FrameMemo memo = frame_memo(st, tail + 256, n_rays > 0);
+    P.pow_global = memo.p;
+    frame_begin(d_stats, qh, n_rays > 0 ? 64 : 0, memo.p, memo.clear, trav, stream);
     if (n_rays == 0) return VRT_OK;
     RayTab tab = ray_tab_at((double*)d_workspace, n_rays);
     hipLaunchKernelGGL(raygen_explicit_kernel, dim3(grid_for(n_rays)), dim3(VRT_BLOCK), 0, stream, *st, cam->lens, d_dir_x, d_dir_y,
@@ -5907,7 +5886,7 @@ int vrt_trace_rays(const vrt_scene* scene, const vrt_settings* st, const vrt_cam
     P.draw_stride = n_draws;
     P.first_draw = (st->dof != 0.0) ? 2 : 0;
     P.rays = d_rays;
-    launch_march<true, false>(P, march_grid(n_rays), 2, false, false, stream);
+    launch_march(P, march_grid(n_rays), 2, false, false, true, false, stream);
     HIP_TRY(hipGetLastError());
     return VRT_OK;
 }
@@ -5975,6 +5954,25 @@ int vrt_diag_last_plan(int64_t* out, int n) {
     if (!out || n < 0) return VRT_ERR_ARG;
     for (int j = 0; j < n && j < VRT_PLAN_WORDS; j++) out[j] = g_plan.w[j];
     return VRT_PLAN_WORDS;
+}
+// Diagnostic, outside include/vrt.h: the instance launch_march runs for the n_in = 16 words of MarchChoiceIn, as march_choose
+// decides.  Returns its status; on VRT_OK the instance's name with every template argument is in name[name_cap] and
+// effects[3] holds what the choice makes of the launch's wt_on and trav_words and whether tile_heads stays set.  Host memory only.
+int vrt_diag_march_variant(const int32_t* in, int n_in, char* name, int name_cap, int32_t* effects) {
+    MarchChoiceIn ci;
+    MarchChoice c;
+    if (!in || n_in != (int)(sizeof ci / sizeof(int32_t)) || !name || name_cap < 1 || !effects) return VRT_ERR_ARG;
+    memcpy(&ci, in, sizeof ci);
+    if (ci.resmode < 0 || ci.resmode > 2 || ci.per_pixel < 0 || ci.per_pixel > 2 || ci.lookup < 0 || ci.lookup > 2 || ci.trav_words < 0) return VRT_ERR_ARG;
+    name[0] = 0;
+    const int rc = march_choose(ci, c);
+    if (rc != VRT_OK) return rc;
+    if ((size_t)name_cap <= strlen(c.k->name)) return VRT_ERR_ARG;
+    strcpy(name, c.k->name);
+    effects[0] = c.wt_on;
+    effects[1] = c.trav_words;
+    effects[2] = ci.tile_heads && c.keep_tile_heads;
+    return VRT_OK;
 }
 
 #ifdef VRT_DIAG
