@@ -14,6 +14,7 @@ from . import _native as nat
 from . import data as _data
 from .lib import vec3, quaternion, rgb, store, is_default_background
 from .scene import PackedScene
+from .results import RenderResult, HitResult, CastResult, ShadeResult, _traversed_positions
 
 
 def _xyz(v):
@@ -21,11 +22,78 @@ def _xyz(v):
 
 
 # why a frame's or a batch's rays are left over (d_stats[VRT_S_RNG_EXHAUSTED]): the capacities of include/vrt.h,
-# vrt_workspace_bytes, restated for the VrtError of render() and render_views() -- keep the two alike
+# vrt_workspace_bytes, restated for the VrtError of _check_stats
 _EXHAUSTED_RULE = ("they consumed more than 1024 random draws (341 rough hits), or a re-trace list of their march launch (at "
                    "most 2**28 ray slots of the %s) was full: more than 4096 rays of the launch needed more than 113 draws, or "
                    "more rays than 1/64 of the launch, held between 2**18 and 2**22 (the whole launch if it is smaller), "
                    "outran the 64-draw table; lower max_bounces or raise material absorption")
+
+
+def _check_stats(stats, draws, what):
+    """What the host statistics (numpy int64[16]) of a "frame" (render) or a "batch" (render_views) marched with `draws`
+    draws per seed ask for.  Returns (retry, draws64): retry -- more rays outran the 32-draw table than the re-trace list
+    holds: render again with 64; draws64 -- use 64 draws per seed from now on (a retry, or many rays were re-traced).
+    Raises VrtError for rays left over at 64 draws and for the internal errors (a batch does not report stalled waves)."""
+    frame = what == "frame"
+    if stats[nat.S_RNG_EXHAUSTED]:
+        if draws == 32:
+            return True, True
+        raise nat.VrtError("%d rays%s could not be completed: %s"
+                           % (int(stats[nat.S_RNG_EXHAUSTED]), "" if frame else " of the batch", _EXHAUSTED_RULE % what))
+    if frame and stats[nat.S_STALLED]:
+        raise nat.VrtError("%d waves of the march found nothing to run and gave up (internal error, frame "
+                           "invalid)" % int(stats[nat.S_STALLED]))
+    if stats[nat.S_TRAV_OUTSIDE]:
+        raise nat.VrtError("%d chunk visits fell outside the traversed %s (internal bound violated)"
+                           % (int(stats[nat.S_TRAV_OUTSIDE]), "box" if frame else "boxes"))
+    # many rays outran the 32-draw table and were re-traced: keep 64 draws per seed from now on
+    return False, bool(draws == 32 and stats[nat.S_RNG_RETRACED] * 50 > max(1, stats[nat.S_RAYS]))
+
+
+def _floats(v, name, who, shape, dev, any_dtype=False):
+    """Argument `name` of `who` -- a torch tensor or whatever numpy takes -- as a float64 tensor on `dev` of `shape`: one
+    entry per dimension, an int for a size that must match, a string for one that is free (and how the message names it).
+    Booleans, strings and integer tensors are refused unless `any_dtype` (lives: converted as they are)."""
+    import torch
+    if isinstance(v, torch.Tensor):
+        if not (any_dtype or v.dtype.is_floating_point):
+            raise ValueError("%s: %s must be floating point, not %s" % (who, name, v.dtype))
+        t = v.to(device=dev, dtype=torch.float64)
+    else:
+        a = np.asarray(v)
+        if not any_dtype and a.dtype.kind not in "fiu":
+            raise ValueError("%s: %s must be numbers, not %s" % (who, name, a.dtype))
+        t = torch.from_numpy(np.array(a, np.float64)).to(dev)
+    if t.dim() != len(shape) or any(isinstance(w, int) and int(g) != w for g, w in zip(t.shape, shape)):
+        raise ValueError("%s: %s must have shape [%s], not %s" % (who, name, ", ".join(str(w) for w in shape), list(t.shape)))
+    return t
+
+
+def _seeds(v, n, who, dev):
+    """Argument `seeds` of `who` as a contiguous int64 tensor [n] on `dev`.  numpy seeds are range-checked; a torch tensor
+    is taken as it is (checking it would synchronise)."""
+    import torch
+    if isinstance(v, torch.Tensor):
+        if v.dtype.is_floating_point or v.dtype == torch.bool:
+            raise ValueError("%s: seeds must be integers, not %s" % (who, v.dtype))
+        t = v.to(device=dev, dtype=torch.int64)
+    else:
+        a = np.asarray(v)
+        if a.dtype.kind not in "iu" or (a.size and (int(a.min()) < 0 or int(a.max()) >= 1 << 63)):
+            raise ValueError("%s: seeds must be integers in [0, 2**63)" % who)
+        t = torch.from_numpy(np.array(a, np.int64)).to(dev)
+    if t.dim() != 1 or int(t.shape[0]) != n:
+        raise ValueError("%s: seeds must have shape [%d], not %s" % (who, n, list(t.shape)))
+    return t.contiguous()
+
+
+def _max_life(max_life, default, who):
+    """The bound on how long a lane may march, as `who` was given it (None: `default`)."""
+    max_life = float(default if max_life is None else max_life)
+    if not (max_life > 0) or max_life > float(1 << 28):
+        raise ValueError("%s: max_life must lie in (0, 2**28], not %r" % (who, max_life))
+    return max_life
+
 
 _POW_MEMOS = set()   # (device index, falloff) pairs for which vrt_pow_memo_create has run in this process
 
@@ -70,196 +138,6 @@ class DevicePixels:
         self.table_streams = set()
 
 
-class RenderResult:
-    """Device-side outputs of one tile render (torch tensors) plus host statistics."""
-
-    def __init__(self):
-        self.rgba_f32 = None     # [n_px, 4] float32: per-pixel mean of [r, g, b, alpha] (before Surface.set_at)
-        self.image_u8 = None     # [H, W, 4] uint8 full-window RGBA, non-owned pixels 0
-        self.ray_rgba = None     # [n_px * max_samples] int32 packed per-sample r|g<<8|b<<16|a<<24
-        self.rays = None         # numpy structured array of per-ray end states (only if requested)
-        self.stats = None        # numpy int64[16]
-        self.traversed_keys = None
-        self.trav_origin = None
-        self.trav_dims = None
-        self.max_samples = 1
-        self.pixels = None
-
-    def counters(self):
-        return {k: int(self.stats[i]) for i, k in enumerate(nat.COUNTER_NAMES)}
-
-    def traversed(self, chunk_size):
-        """Visited chunk positions in the reference's order (order-preserving union over rays in call order,
-        reference init.py:72-73, 143; lib.py:404-409)."""
-        import torch
-        if self.traversed_keys is None:
-            return []
-        k = self.traversed_keys
-        idx = torch.nonzero(k != -1).flatten()
-        if idx.numel() == 0:
-            return []
-        order = torch.argsort(k[idx])
-        idx = idx[order].cpu().numpy()
-        d = self.trav_dims
-        cz = idx % d[2]
-        cy = (idx // d[2]) % d[1]
-        cx = idx // (d[2] * d[1])
-        o = self.trav_origin
-        return [(float(o[0] + a * chunk_size), float(o[1] + b * chunk_size), float(o[2] + c * chunk_size))
-                for a, b, c in zip(cx.tolist(), cy.tolist(), cz.tolist())]
-
-
-class HitResult:
-    """Device-side records of a first-hit pass (Camera.first_hit / first_hit_views): what every primary ray of the frame sees.
-    `step`, `pos`, `cell` and `material` are views of one buffer of 48-byte vrt_hit records (include/vrt.h), one per ray
-    slot p * max_samples + s (`samples` == max_samples) or one per pixel (`samples` == 1: every pixel's first sample)."""
-
-    def __init__(self, records, pixels, samples, max_samples, height, width, stats_dev):
-        import torch
-        n = records.numel() // nat.HIT_BYTES
-        f64 = records.view(torch.float64).view(n, nat.HIT_BYTES // 8)
-        i32 = records.view(torch.int32).view(n, nat.HIT_BYTES // 4)
-        self.records = records           # uint8 [n * 48]
-        self.step = f64[:, 0]            # float64 [n]: ray.step at the first voxel, or >= the ray's life for a miss
-        self.pos = f64[:, 1:4]           # float64 [n, 3]: ray.pos at that moment
-        self.cell = i32[:, 8:11]         # int32 [n, 3]: floor(pos)
-        self.material = i32[:, 11]       # int32 [n]: 1..255 the material found, 0 none, -1 unused sample slot
-        self.pixels = pixels             # numpy [n_px, 2] (x, y)
-        self.samples = samples
-        self.max_samples = max_samples
-        self.height, self.width = height, width
-        self._stats_dev = stats_dev
-        self._stats = None
-
-    @property
-    def stats(self):
-        """numpy int64[16], copied from the device on first use (a synchronisation): word 8 = rays traced, word 4 = rays that
-        found a voxel.  A batch's views share one block: the batch's totals."""
-        if self._stats is None:
-            self._stats = self._stats_dev.cpu().numpy()
-        return self._stats
-
-    def numpy(self):
-        """The records as a numpy structured array (fields step, pos, cell, material)."""
-        return self.records.cpu().numpy().view(np.dtype(nat.HIT_FIELDS))
-
-    def _scatter(self, values, fill, dtype):
-        import torch
-        img = torch.full((self.height, self.width), fill, dtype=dtype, device=self.records.device)
-        px = torch.from_numpy(self.pixels.astype(np.int64)).to(self.records.device)
-        img[px[:, 1], px[:, 0]] = values[:: self.samples]
-        return img
-
-    def depth_image(self):
-        """[height, width] float64: sample 0's step where it found a voxel, inf where it found none and at pixels that
-        are not listed."""
-        import torch
-        inf = torch.full_like(self.step, float("inf"))
-        return self._scatter(torch.where(self.material > 0, self.step, inf), float("inf"), torch.float64)
-
-    def material_image(self):
-        """[height, width] int32: the material id sample 0 found (0: none); -1 at pixels that are not listed."""
-        import torch
-        return self._scatter(self.material, -1, torch.int32)
-
-
-class CastResult:
-    """Device-side records of Camera.cast_rays: what every explicit ray found.  `step`, `pos`, `cell` and `material` are
-    views of one buffer of 48-byte vrt_hit records (include/vrt.h), record k for ray k."""
-
-    def __init__(self, records, stats_dev):
-        import torch
-        n = records.numel() // nat.HIT_BYTES
-        f64 = records.view(torch.float64).view(n, nat.HIT_BYTES // 8)
-        i32 = records.view(torch.int32).view(n, nat.HIT_BYTES // 4)
-        self.records = records           # uint8 [n * 48]
-        self.step = f64[:, 0]            # float64 [n]: ray.step at the first voxel, or >= the ray's life for a miss
-        self.pos = f64[:, 1:4]           # float64 [n, 3]: ray.pos at that moment
-        self.cell = i32[:, 8:11]         # int32 [n, 3]: floor(pos)
-        self.material = i32[:, 11]       # int32 [n]: 1..255 the material found, 0 none, -2 the ray was rejected
-        self._stats_dev = stats_dev
-        self._stats = None
-
-    @property
-    def stats(self):
-        """numpy int64[16], copied from the device on first use (a synchronisation): word 8 = rays marched, word 4 = rays
-        that found a voxel, word 9 = rays rejected."""
-        if self._stats is None:
-            self._stats = self._stats_dev.cpu().numpy()
-        return self._stats
-
-    def numpy(self):
-        """The records as a numpy structured array (fields step, pos, cell, material)."""
-        return self.records.cpu().numpy().view(np.dtype(nat.HIT_FIELDS))
-
-    def hit_mask(self):
-        """torch.bool [n]: the ray found a voxel within its life."""
-        return self.material > 0
-
-    def rejected_mask(self):
-        """torch.bool [n]: the ray was rejected on the device (not finite, life > max_life, |vel| > 2**25, or out of
-        range: include/vrt.h, vrt_cast_ray) and was not marched."""
-        return self.material == nat.HIT_REJECTED
-
-
-class ShadeResult:
-    """Device-side outputs of Camera.shade_rays: what colour and energy arrived along every explicit ray.  `rgba` is packed
-    r | g << 8 | b << 16 | alpha << 24, entry k for ray k; `records` (or None) one buffer of 152-byte vrt_ray records
-    (include/vrt.h), whose `s` field is 0 for a completed ray, -2 for a rejected one and -3 for one whose draws ran out."""
-
-    def __init__(self, rgba, records, stats_dev, trav=None):
-        self.rgba = rgba                 # uint32 [n]
-        self.records = records           # uint8 [n * 152], or None
-        self._stats_dev = stats_dev
-        self._stats = None
-        self.traversed_keys, self.trav_origin, self.trav_dims = trav if trav is not None else (None, None, None)
-
-    @property
-    def stats(self):
-        """numpy int64[16], copied from the device on first use (a synchronisation): words 0..7 event sums over completed
-        rays, 8 completed rays, 9 rejected, 10 rays whose draws ran out, 11 chunk visits outside the traversed box."""
-        if self._stats is None:
-            self._stats = self._stats_dev.cpu().numpy()
-        return self._stats
-
-    def _s(self, what):
-        import torch
-        if self.records is None:
-            raise ValueError("%s needs the records (shade_rays(..., want_records=True))" % what)
-        n = self.records.numel() // nat.RAY_BYTES
-        return self.records.view(torch.int32).view(n, nat.RAY_BYTES // 4)[:, 2]
-
-    def numpy(self):
-        """The records as a numpy structured array of vrt_ray (fields x, y, s, color, alpha, ntrav, counters, detail,
-        energy, step, life, bounces, pos, vel)."""
-        if self.records is None:
-            raise ValueError("numpy() needs the records (shade_rays(..., want_records=True))")
-        return self.records.cpu().numpy().view(np.dtype(nat.RAY_FIELDS, align=True))
-
-    def rejected_mask(self):
-        """torch.bool [n]: the ray was rejected on the device (cast_rays's rule) and was not marched."""
-        return self._s("rejected_mask()") == nat.RAY_REJECTED
-
-    def exhausted_mask(self):
-        """torch.bool [n]: the ray needed more draws than it was given and was not completed: repeat it with a longer row."""
-        return self._s("exhausted_mask()") == nat.RAY_EXHAUSTED
-
-    def image(self, height, width):
-        """[height, width, 4] uint8 RGBA from n == height * width rays in row-major order (ray y * width + x is pixel (x, y))."""
-        import torch
-        height, width = int(height), int(width)
-        if height <= 0 or width <= 0 or height * width != int(self.rgba.numel()):
-            raise ValueError("image(%d, %d): %d rays are not %d x %d pixels" % (height, width, int(self.rgba.numel()), height, width))
-        return self.rgba.view(torch.uint8).view(height, width, 4)
-
-    def traversed(self, chunk_size):
-        """Visited chunk positions inside the box the call was given, in the reference's order (the order-preserving union
-        over the rays in array order); [] without a box."""
-        rr = RenderResult()
-        rr.traversed_keys, rr.trav_origin, rr.trav_dims = self.traversed_keys, self.trav_origin, self.trav_dims
-        return rr.traversed(chunk_size)
-
-
 class Camera:
     def __init__(self, settings=None, device=None):
         import torch
@@ -280,6 +158,7 @@ class Camera:
         self._world = None
         self._camera_table = None
         self._camera_table_max_res = 0
+        self._views_cams = None   # (records as bytes, their device copy) of the last batch of poses: _device_poses
         self.last_stats = None
         self.fast_draws = 32   # draws per seed in the frame table (32 | 64): speed only, auto-raised by render()
         # static seeds (settings.static, the reference default) make every frame's random draws -- and with them the
@@ -354,14 +233,13 @@ class Camera:
         run use multigpu.chunk_update_all_ranks, which unions the keys over the ranks first."""
         torch = self._torch
         L = nat.lib()
-        if getattr(self, "_world", None) is None:
+        if self._world is None:
             raise RuntimeError("chunk_update() needs set_world_scene() first")
         s = self._settings()
         w = self._world
         cs = int(s.chunk_size)
         dev = self._require_device()
-        tr = nat.VrtTraversed()
-        keys = None
+        box = ()   # (origin, dims, keys) of what was traversed
         if isinstance(traversed, (list, tuple)) and traversed and all(isinstance(t, RenderResult) for t in traversed):
             from .multigpu import merge_traversed
             with_keys = [t for t in traversed if t.traversed_keys is not None]
@@ -374,9 +252,7 @@ class Camera:
             traversed = merged
         if isinstance(traversed, RenderResult):
             if traversed.traversed_keys is not None:
-                keys = traversed.traversed_keys
-                tr.origin[:] = traversed.trav_origin
-                tr.dims[:] = traversed.trav_dims
+                box = (traversed.trav_origin, traversed.trav_dims, traversed.traversed_keys)
         elif traversed:
             pts = np.asarray([[int(v) for v in p] for p in traversed], np.int64).reshape(-1, 3)
             lo = pts.min(0)
@@ -384,11 +260,8 @@ class Camera:
             host = np.full(tuple(d), -1, np.int64)
             c = (pts - lo) // cs
             host[c[:, 0], c[:, 1], c[:, 2]] = 0
-            keys = torch.from_numpy(host.reshape(-1)).to(dev)
-            tr.origin[:] = [int(v) for v in lo]
-            tr.dims[:] = [int(v) for v in d]
-        if keys is not None:
-            tr.d_keys = keys.data_ptr()
+            box = ([int(v) for v in lo], [int(v) for v in d], torch.from_numpy(host.reshape(-1)).to(dev))
+        tr, keys = self._key_box(*box)   # (`keys` stays alive until the launch below has been made)
         if self._camera_table is None:
             self._camera_table = torch.zeros_like(w.device_tensors["chunk_table"])
         origin = (C.c_int64 * 3)(*[int(v) for v in w.origin])
@@ -447,14 +320,13 @@ class Camera:
         cs.chunk_size = sc.chunk_size
         cs.n_slots = sc.n_slots
         cs.n_materials = len(sc.materials)
-        cam_table = getattr(self, "_camera_table", None)
-        cs.d_chunk_table = (cam_table if cam_table is not None and sc is getattr(self, "_world", None)
-                            else t["chunk_table"]).data_ptr()
+        selected = self._camera_table is not None and sc is self._world   # chunk_update() chose this world's chunks
+        cs.d_chunk_table = (self._camera_table if selected else t["chunk_table"]).data_ptr()
         cs.d_voxels = t["voxels"].data_ptr()
         cs.d_materials = t["materials"].data_ptr()
         cs.d_occupancy = t["occupancy"].data_ptr() if t.get("occupancy") is not None else None
         cs.d_world_tables = t["world_tables"].data_ptr() if t.get("world_tables") is not None else None
-        if cam_table is not None and sc is getattr(self, "_world", None):
+        if selected:
             cs.max_resolution = int(self._camera_table_max_res)   # (as of the chunk_update() that wrote the table)
             # (vrt_select_chunks keeps every block where it is: a table-order world stays one)
             cs.flags = nat.SCENE_LAYOUT_DENSE if sc.dense else 0
@@ -488,39 +360,55 @@ class Camera:
         lod = min(int(math.trunc(q * (1 + 1e-12))), lod_max)
         return lod + 1
 
-    def _velocity_bound(self):
-        """Upper bound of |vel|_inf of a ray.  After a hit the velocity is Chebyshev-normalised and a reflection
+    def _velocity_bound(self, rot=None):
+        """Upper bound of |vel|_inf of a ray of a camera with rotation `rot` ((x, y, z, w); default: this camera's).  After a hit the velocity is Chebyshev-normalised and a reflection
         scales a component by |1 - 2 ior| <= 1 (init.py:84, 108), but the primary direction is
         rot.multiply(lens quaternion).vec_forward() (lib.py:353-358, 372-376) and the reference's quaternion product is
         not the Hamilton product: it does not preserve the norm, so for a rotated camera the primary velocity can be
         longer than 1 (1.65 seen).  With r = M(rot) o, |o| = 1: |vx|, |vy| <= |r|^2 and |vz| <= max(1, 2 |r|^2 - 1)."""
-        qx, qy, qz, qw = [float(v) for v in (self.rot.x, self.rot.y, self.rot.z, self.rot.w)]
+        qx, qy, qz, qw = [float(v) for v in (rot if rot is not None else (self.rot.x, self.rot.y, self.rot.z, self.rot.w))]
         m = np.array([[qw, qz, -qy, qx], [qz, qw, qx, qy], [qy, -qx, qw, qz], [qx, -qy, -qz, qw]])
         s2 = float(np.linalg.norm(m, 2)) ** 2
         return max(1.0, s2, 2.0 * s2 - 1.0)
 
-    def _trav_box(self, want):
-        """Box of chunk cells around the camera that every ray stays inside: a ray moves at most dist_max (plus one
-        void-skip step of at most 1 + chunk_size / 2) times _velocity_bound() in the max-norm."""
-        torch = self._torch
-        tr = nat.VrtTraversed()
-        if not want:
-            return tr, None
+    def _box_radius(self, rot=None):
+        """Chunk cells on either side of a camera's own that every ray stays inside: a ray moves at most dist_max (plus one
+        void-skip step of at most 1 + chunk_size / 2) times _velocity_bound(rot) in the max-norm."""
         s = self._settings()
         cs = int(s.chunk_size)
-        reach = (float(s.dist_max) + 1.0 + cs / 2.0) * self._velocity_bound()
-        r = int(math.ceil(reach / cs)) + 1
-        if (2 * r + 1) ** 3 > (1 << 28):
-            raise nat.VrtError("the traversed-chunk box would need %d^3 cells (dist_max %r, chunk_size %d, camera "
-                               "rotation %r)" % (2 * r + 1, s.dist_max, cs, self.rot))
-        o = [int(math.floor(v / cs)) - r for v in _xyz(self.pos)]
-        n = 2 * r + 1
-        keys = torch.empty((n * n * n,), dtype=torch.int64, device=self._device)
-        tr.origin[:] = [v * cs for v in o]
-        tr.dims[:] = [n, n, n]
-        tr.reset = 1          # (vrt_render_tile sets every key to "never visited" in the launch that clears its counters)
+        return int(math.ceil((float(s.dist_max) + 1.0 + cs / 2.0) * self._velocity_bound(rot) / cs)) + 1
+
+    def _box_around(self, pos, r):
+        """(origin, dims) of the box of `r` chunk cells on either side of the one that holds `pos` (x, y, z)."""
+        cs = int(self._settings().chunk_size)
+        return [(int(math.floor(v / cs)) - r) * cs for v in pos], [2 * r + 1] * 3
+
+    def _key_box(self, origin=None, dims=None, keys=None, reset=0):
+        """(vrt_traversed, keys) for the box of `dims` chunk cells whose cell (0, 0, 0) is the chunk at `origin` (world
+        coordinates); without an origin: no box.  `keys`: the caller's int64 tensor, one key per cell, used as it is unless
+        `reset`; None: allocated here, and the launch that clears its counters sets every key to "never visited"."""
+        tr = nat.VrtTraversed()
+        if origin is None:
+            return tr, None
+        if keys is None:
+            keys = self._torch.empty((dims[0] * dims[1] * dims[2],), dtype=self._torch.int64, device=self._device)
+            reset = 1
+        tr.origin[:] = origin
+        tr.dims[:] = dims
+        tr.reset = reset
         tr.d_keys = keys.data_ptr()
         return tr, keys
+
+    def _trav_box(self, want):
+        """Box of chunk cells around the camera that every ray stays inside (_box_radius)."""
+        if not want:
+            return self._key_box()
+        r = self._box_radius()
+        if (2 * r + 1) ** 3 > (1 << 28):
+            s = self._settings()
+            raise nat.VrtError("the traversed-chunk box would need %d^3 cells (dist_max %r, chunk_size %d, camera "
+                               "rotation %r)" % (2 * r + 1, s.dist_max, int(s.chunk_size), self.rot))
+        return self._key_box(*self._box_around(_xyz(self.pos), r))
 
     def upload_pixels(self, pixels):
         """Validate and upload an [n, 2] (x, y) pixel list once; pass the result as `pixels=` to render()."""
@@ -647,6 +535,30 @@ class Camera:
             cur.wait_event(ev)
         dp.table_streams.add(int(cur.cuda_stream))
 
+    def _tables_for(self, dp, st, fast_draws):
+        """(draw table, ray table) of `dp` for a static-seed run, built or cached, with the current stream ordered behind
+        their builds."""
+        table = self._draw_table_for(dp, st, fast_draws)
+        self._order_after_table_builds(dp)   # (the ray table's build reads the draw table)
+        rtab = self._ray_table_for(dp, st, fast_draws, table)
+        self._order_after_table_builds(dp)
+        return table, rtab
+
+    def _frame_setup(self, thread, pixels, seed_nonce=0):
+        """What every frame entry point starts from: (pixel list with its plan, C settings, C scene, max samples per pixel,
+        pixels).  The plan of a new pixel list is built on the stream that is current."""
+        dev = self._require_device()
+        sc = self._ensure_scene()
+        st = self._c_settings(seed_nonce)
+        with self._torch.cuda.device(dev):
+            dp = self._plan_for(self._pixels_tensor(thread, pixels), st)
+        return dp, st, self._c_scene(sc), nat.lib().vrt_max_samples(C.byref(st)), int(dp.array.shape[0])
+
+    def _on_stream(self, stream):
+        """Context of a call that takes `stream=`: that torch stream is current inside; None: the current one stays."""
+        torch = self._torch
+        return torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream())
+
     def _get_workspace(self, nbytes):
         """Scratch buffer of the frame being rendered: one per stream, so that frames submitted on different streams
         (two frames in flight: the second starts while the first one's last waves drain) never share it."""
@@ -666,17 +578,11 @@ class Camera:
         host except the 16-word statistics block (when `check`)."""
         torch = self._torch
         L = nat.lib()
-        dev = self._require_device()
+        dp, st, csc, smax, n_px = self._frame_setup(thread, pixels, seed_nonce)
+        dev = self._device
         s = self._settings()
-        sc = self._ensure_scene()
-        st = self._c_settings(seed_nonce)
-        with torch.cuda.device(dev):
-            dp = self._plan_for(self._pixels_tensor(thread, pixels), st)
         d_px, arr = dp.tensor, dp.array
-        n_px = int(arr.shape[0])
         cam = self._c_camera()
-        csc = self._c_scene(sc)
-        smax = L.vrt_max_samples(C.byref(st))
         nb = C.c_int64(0)
         used_draws = self.fast_draws
         cached = bool(self.cache_draws and s.static and int(st.seed_nonce) == 0)
@@ -706,10 +612,7 @@ class Camera:
             tr, keys = self._trav_box(want_traversed)
             table = rtab = None
             if cached:
-                table = self._draw_table_for(dp, st, used_draws)
-                self._order_after_table_builds(dp)   # (the ray table's build reads the draw table)
-                rtab = self._ray_table_for(dp, st, used_draws, table)
-                self._order_after_table_builds(dp)
+                table, rtab = self._tables_for(dp, st, used_draws)
             rc = L.vrt_render_tile(C.byref(csc), C.byref(st), C.byref(cam), d_px.data_ptr(), n_px, dp.plan.data_ptr(),
                                    n_rows, used_draws, table.data_ptr() if table is not None else None,
                                    rtab.data_ptr() if rtab is not None else None, ws.data_ptr(), ws.numel(),
@@ -726,24 +629,13 @@ class Camera:
             if check or want_rays:
                 res.stats = stats.cpu().numpy()
                 self.last_stats = res.stats
-                if res.stats[nat.S_RNG_EXHAUSTED]:
-                    if used_draws == 32:
-                        # more rays outran the 32-draw table than the re-trace list holds: render again with 64
-                        self.fast_draws = 64
-                        return self.render(thread, pixels=dp, want_image=want_image, want_f32=want_f32,
-                                           want_ray_rgba=want_ray_rgba, want_rays=want_rays,
-                                           want_traversed=want_traversed, seed_nonce=int(st.seed_nonce), check=check)
-                    raise nat.VrtError("%d rays could not be completed: %s"
-                                       % (int(res.stats[nat.S_RNG_EXHAUSTED]), _EXHAUSTED_RULE % "frame"))
-                if res.stats[nat.S_STALLED]:
-                    raise nat.VrtError("%d waves of the march found nothing to run and gave up (internal error, frame "
-                                       "invalid)" % int(res.stats[nat.S_STALLED]))
-                if res.stats[nat.S_TRAV_OUTSIDE]:
-                    raise nat.VrtError("%d chunk visits fell outside the traversed box (internal bound violated)"
-                                       % int(res.stats[nat.S_TRAV_OUTSIDE]))
-                # many rays outran the 32-draw table and were re-traced: keep 64 draws per seed from now on
-                if used_draws == 32 and res.stats[nat.S_RNG_RETRACED] * 50 > max(1, res.stats[nat.S_RAYS]):
+                retry, draws64 = _check_stats(res.stats, used_draws, "frame")
+                if draws64:
                     self.fast_draws = 64
+                if retry:
+                    return self.render(thread, pixels=dp, want_image=want_image, want_f32=want_f32,
+                                       want_ray_rgba=want_ray_rgba, want_rays=want_rays,
+                                       want_traversed=want_traversed, seed_nonce=int(st.seed_nonce), check=check)
             if want_rays:
                 raw = d_rays.cpu().numpy()
                 res.rays = raw.view(np.dtype(nat.RAY_FIELDS, align=True))
@@ -790,6 +682,31 @@ class Camera:
         if not np.all(np.abs(rec[:, :3]).max(1) + reach < 2.0 ** 28):
             raise ValueError("a pose of the batch lies outside the range the march supports: |pos| + reach must stay below 2**28")
 
+    def _device_poses(self, rec, who, verb):
+        """The device copy of the pose records `rec`.  Their upload is a host-to-device copy, which a stream capture cannot
+        hold: the last batch's device copy is kept (self._views_cams) and reused for equal poses, whichever of the batch
+        calls made it (a capture follows a warm-up batch with the poses it captures)."""
+        torch = self._torch
+        ckey = rec.tobytes()
+        if self._views_cams is None or self._views_cams[0] != ckey:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("%s() inside a stream capture needs the poses of the batch %s just before "
+                                   "it (their upload cannot be captured)" % (who, verb))
+            self._views_cams = (ckey, torch.from_numpy(rec).to(self._device))
+        return self._views_cams[1]
+
+    def _view_boxes(self, rec):
+        """(origins, dims) of the traversed boxes of a batch: every view's box by _trav_box's rule for its pose; the velocity
+        bound depends on the rotation, so all of them get the largest dimensions of the batch (the library wants equal dims
+        and one allocation of keys)."""
+        r = max(self._box_radius(q) for q in rec[:, 3:7])
+        n, n_views = 2 * r + 1, int(rec.shape[0])
+        if n ** 3 > (1 << 28) or n ** 3 * n_views >= (1 << 32):
+            s = self._settings()
+            raise nat.VrtError("the traversed-chunk boxes would need %d x %d^3 cells (dist_max %r, chunk_size %d)"
+                               % (n_views, n, s.dist_max, int(s.chunk_size)))
+        return [self._box_around(p, r)[0] for p in rec[:, :3]], [n, n, n]
+
     def render_views(self, poses, thread=0, pixels=None, want_image=True, want_f32=True, want_ray_rgba=False,
                      want_traversed=True, check=True):
         """Camera.render for many camera poses of one scene with one march launch per batch instead of per view (plus the
@@ -814,15 +731,9 @@ class Camera:
         rec = self._pose_records(poses, self.lens)
         self._check_pose_range(rec, s)
         n_views = int(rec.shape[0])
-        dev = self._require_device()
-        sc = self._ensure_scene()
-        st = self._c_settings(0)
-        with torch.cuda.device(dev):
-            dp = self._plan_for(self._pixels_tensor(thread, pixels), st)
+        dp, st, csc, smax, n_px = self._frame_setup(thread, pixels)
+        dev = self._device
         d_px, arr = dp.tensor, dp.array
-        n_px = int(arr.shape[0])
-        csc = self._c_scene(sc)
-        smax = L.vrt_max_samples(C.byref(st))
         slots = n_px * smax
         if n_views * slots >= (1 << 32) - 1:
             raise nat.VrtError("the batch is too large: views * pixels * samples must stay below 2**32 (%d * %d)"
@@ -832,7 +743,6 @@ class Camera:
         nat.check(L.vrt_views_workspace_bytes(C.byref(st), n_views, n_px, C.byref(nb)), "vrt_views_workspace_bytes")
         _ensure_pow_memo(torch, dev, s.falloff)
         ws = self._get_workspace(nb.value)
-        cs = int(s.chunk_size)
         H, W = int(s.height), int(s.width)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream().cuda_stream
@@ -841,46 +751,14 @@ class Camera:
                 if want_image else None
             rr = torch.empty((n_views, slots), dtype=torch.int32, device=dev) if want_ray_rgba else None
             stats = torch.empty(nat.NSTATS, dtype=torch.int64, device=dev)   # (the library clears it)
-            # the records' upload is a host-to-device copy, which a stream capture cannot hold: the last batch's device
-            # copy is kept and reused for equal poses (a capture follows a warm-up batch with the poses it captures)
-            ckey = rec.tobytes()
-            hit = getattr(self, "_views_cams", None)
-            if hit is not None and hit[0] == ckey:
-                cams = hit[1]
-            elif torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("render_views() inside a stream capture needs the poses of the batch rendered just before "
-                                   "it (their upload cannot be captured)")
-            else:
-                cams = torch.from_numpy(rec).to(dev)
-                self._views_cams = (ckey, cams)
-            # every view's box by _trav_box's rule for its pose; the velocity bound depends on the rotation, so all of
-            # them get the largest dimensions of the batch (the library wants equal dims and one allocation of keys)
+            cams = self._device_poses(rec, "render_views", "rendered")
             trs = keys = None
             if want_traversed:
-                keep = (self.pos, self.rot)
-                try:
-                    r = 0
-                    for v in range(n_views):
-                        self.rot = quaternion(*rec[v, 3:7])
-                        reach = (float(s.dist_max) + 1.0 + cs / 2.0) * self._velocity_bound()
-                        r = max(r, int(math.ceil(reach / cs)) + 1)
-                finally:
-                    self.pos, self.rot = keep
-                n = 2 * r + 1
-                if n ** 3 > (1 << 28) or n ** 3 * n_views >= (1 << 32):
-                    raise nat.VrtError("the traversed-chunk boxes would need %d x %d^3 cells (dist_max %r, chunk_size %d)"
-                                       % (n_views, n, s.dist_max, cs))
-                keys = torch.empty((n_views, n * n * n), dtype=torch.int64, device=dev)
-                trs = (nat.VrtTraversed * n_views)()
-                for v in range(n_views):
-                    trs[v].origin[:] = [(int(math.floor(p / cs)) - r) * cs for p in rec[v, :3]]
-                    trs[v].dims[:] = [n, n, n]
-                    trs[v].reset = 1
-                    trs[v].d_keys = keys[v].data_ptr()
-            table = self._draw_table_for(dp, st, used_draws)
-            self._order_after_table_builds(dp)   # (the ray table's build reads the draw table)
-            rtab = self._ray_table_for(dp, st, used_draws, table)
-            self._order_after_table_builds(dp)
+                origins, dims = self._view_boxes(rec)
+                keys = torch.empty((n_views, dims[0] * dims[1] * dims[2]), dtype=torch.int64, device=dev)
+                # (the library takes an array of structs: its elements are copies of _key_box's)
+                trs = (nat.VrtTraversed * n_views)(*[self._key_box(o, dims, keys[v], 1)[0] for v, o in enumerate(origins)])
+            table, rtab = self._tables_for(dp, st, used_draws)
             rc = L.vrt_render_views(C.byref(csc), C.byref(st), cams.data_ptr(), n_views, d_px.data_ptr(), n_px,
                                     dp.plan.data_ptr(), dp.n_distinct, used_draws, table.data_ptr(), rtab.data_ptr(),
                                     ws.data_ptr(), ws.numel(), f32.data_ptr() if want_f32 else None,
@@ -891,19 +769,12 @@ class Camera:
             if check:
                 hstats = stats.cpu().numpy()
                 self.last_stats = hstats
-                if hstats[nat.S_RNG_EXHAUSTED]:
-                    if used_draws == 32:
-                        # more rays outran the 32-draw table than the re-trace list holds: render again with 64
-                        self.fast_draws = 64
-                        return self.render_views(rec[:, :7], thread, pixels=dp, want_image=want_image, want_f32=want_f32,
-                                                 want_ray_rgba=want_ray_rgba, want_traversed=want_traversed, check=check)
-                    raise nat.VrtError("%d rays of the batch could not be completed: %s"
-                                       % (int(hstats[nat.S_RNG_EXHAUSTED]), _EXHAUSTED_RULE % "batch"))
-                if hstats[nat.S_TRAV_OUTSIDE]:
-                    raise nat.VrtError("%d chunk visits fell outside the traversed boxes (internal bound violated)"
-                                       % int(hstats[nat.S_TRAV_OUTSIDE]))
-                if used_draws == 32 and hstats[nat.S_RNG_RETRACED] * 50 > max(1, hstats[nat.S_RAYS]):
+                retry, draws64 = _check_stats(hstats, used_draws, "batch")
+                if draws64:
                     self.fast_draws = 64
+                if retry:
+                    return self.render_views(rec[:, :7], thread, pixels=dp, want_image=want_image, want_f32=want_f32,
+                                             want_ray_rgba=want_ray_rgba, want_traversed=want_traversed, check=check)
             out = []
             for v in range(n_views):
                 res = RenderResult()
@@ -928,10 +799,7 @@ class Camera:
         """The plan and the ray table a first-hit pass reads (the lens jitter and the life of every ray are the static-seed
         frame's).  Returns (ray table, retire): with cache_draws unset the tables were built for this call and `retire()`
         drops them again once the pass has been launched."""
-        table = self._draw_table_for(dp, st, self.fast_draws)
-        self._order_after_table_builds(dp)   # (the ray table's build reads the draw table)
-        rtab = self._ray_table_for(dp, st, self.fast_draws, table)
-        self._order_after_table_builds(dp)
+        rtab = self._tables_for(dp, st, self.fast_draws)[1]
 
         def retire():
             if self.cache_draws:
@@ -951,14 +819,10 @@ class Camera:
         L = nat.lib()
         dev = self._require_device()
         s = self._settings()
-        sc = self._ensure_scene()
-        st = self._c_settings(0)
-        with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
-            dp = self._plan_for(self._pixels_tensor(thread, pixels), st)
-            n_px = int(dp.array.shape[0])
+        self._ensure_scene()   # (a changed scene is uploaded on the caller's stream, as render() does, not on `stream`)
+        with torch.cuda.device(dev), self._on_stream(stream):
+            dp, st, csc, smax, n_px = self._frame_setup(thread, pixels)
             cam = self._c_camera()
-            csc = self._c_scene(sc)
-            smax = L.vrt_max_samples(C.byref(st))
             samples = smax if all_samples else 1
             rtab, retire = self._first_hit_tables(dp, st)
             records = torch.empty(max(n_px * samples, 1) * nat.HIT_BYTES, dtype=torch.uint8, device=dev)
@@ -983,27 +847,14 @@ class Camera:
         self._check_pose_range(rec, s)
         n_views = int(rec.shape[0])
         dev = self._require_device()
-        sc = self._ensure_scene()
-        st = self._c_settings(0)
-        with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
-            dp = self._plan_for(self._pixels_tensor(thread, pixels), st)
-            n_px = int(dp.array.shape[0])
-            csc = self._c_scene(sc)
-            smax = L.vrt_max_samples(C.byref(st))
+        self._ensure_scene()   # (on the caller's stream: first_hit)
+        with torch.cuda.device(dev), self._on_stream(stream):
+            dp, st, csc, smax, n_px = self._frame_setup(thread, pixels)
             if n_views * n_px * smax >= (1 << 32) - 1:
                 raise nat.VrtError("the batch is too large: views * pixels * samples must stay below 2**32 (%d * %d)"
                                    % (n_views, n_px * smax))
             samples = smax if all_samples else 1
-            ckey = rec.tobytes()
-            hit = getattr(self, "_views_cams", None)
-            if hit is not None and hit[0] == ckey:
-                cams = hit[1]
-            elif torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("first_hit_views() inside a stream capture needs the poses of the batch made just before "
-                                   "it (their upload cannot be captured)")
-            else:
-                cams = torch.from_numpy(rec).to(dev)
-                self._views_cams = (ckey, cams)
+            cams = self._device_poses(rec, "first_hit_views", "made")
             nb = C.c_int64(0)
             nat.check(L.vrt_first_hit_views_workspace_bytes(n_views, C.byref(nb)), "vrt_first_hit_views_workspace_bytes")
             ws = self._get_workspace(nb.value)
@@ -1025,13 +876,9 @@ class Camera:
         """[n, 8] float64 device tensor of vrt_cast_ray records from what cast_rays (or shade_rays: `who`) was given."""
         torch = self._torch
         dev = self._require_device()
-
-        def is_t(v):
-            return isinstance(v, torch.Tensor)
-
         if velocities is None:
             # ready records, used as they are
-            if not is_t(origins) or origins.dtype != torch.float64 or not origins.is_cuda:
+            if not isinstance(origins, torch.Tensor) or origins.dtype != torch.float64 or not origins.is_cuda:
                 raise ValueError(who + "(records): the records must be one float64 CUDA tensor [n, 8]")
             if origins.dim() != 2 or origins.shape[1] != 8 or not origins.is_contiguous() or origins.data_ptr() % 64:
                 raise ValueError(who + "(records): the records must be a contiguous, 64-byte aligned [n, 8] tensor")
@@ -1040,34 +887,15 @@ class Camera:
             if lives is not None:
                 raise ValueError(who + "(records): ready records carry their own lives")
             return origins
-        parts = []
-        for name, v in (("origins", origins), ("velocities", velocities)):
-            if is_t(v):
-                if not v.dtype.is_floating_point:
-                    raise ValueError(who + ": %s must be floating point, not %s" % (name, v.dtype))
-                v = v.to(device=dev, dtype=torch.float64)
-            else:
-                a = np.asarray(v)
-                if a.dtype.kind not in "fiu":
-                    raise ValueError(who + ": %s must be numbers, not %s" % (name, a.dtype))
-                v = torch.from_numpy(np.array(a, np.float64)).to(dev)
-            if v.dim() != 2 or v.shape[1] != 3:
-                raise ValueError(who + ": %s must have shape [n, 3], not %s" % (name, list(v.shape)))
-            parts.append(v)
-        n = int(parts[0].shape[0])
-        if int(parts[1].shape[0]) != n:
-            raise ValueError(who + ": %d origins but %d velocities" % (n, int(parts[1].shape[0])))
+        org = _floats(origins, "origins", who, ("n", 3), dev)
+        vel = _floats(velocities, "velocities", who, ("n", 3), dev)
+        n = int(org.shape[0])
+        if int(vel.shape[0]) != n:
+            raise ValueError(who + ": %d origins but %d velocities" % (n, int(vel.shape[0])))
         rec = torch.zeros((n, 8), dtype=torch.float64, device=dev)
-        rec[:, 0:3] = parts[0]
-        rec[:, 3:6] = parts[1]
-        if lives is None:
-            rec[:, 6] = float(default_life)
-        else:
-            lv = lives.to(device=dev, dtype=torch.float64) if is_t(lives) else \
-                torch.from_numpy(np.array(lives, np.float64)).to(dev)
-            if lv.dim() != 1 or int(lv.shape[0]) != n:
-                raise ValueError(who + ": lives must have shape [%d], not %s" % (n, list(lv.shape)))
-            rec[:, 6] = lv
+        rec[:, 0:3] = org
+        rec[:, 3:6] = vel
+        rec[:, 6] = float(default_life) if lives is None else _floats(lives, "lives", who, (n,), dev, any_dtype=True)
         return rec
 
     def cast_rays(self, origins, velocities=None, lives=None, max_life=None, stream=None):
@@ -1088,14 +916,10 @@ class Camera:
         L = nat.lib()
         dev = self._require_device()
         s = self._settings()
-        if max_life is None:
-            max_life = float(s.dist_max)
-        max_life = float(max_life)
-        if not (max_life > 0) or max_life > float(1 << 28):
-            raise ValueError("cast_rays: max_life must lie in (0, 2**28], not %r" % max_life)
+        max_life = _max_life(max_life, s.dist_max, "cast_rays")
         sc = self._ensure_scene()
         st = self._c_settings(0)
-        with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        with torch.cuda.device(dev), self._on_stream(stream):
             rec = self._cast_records(origins, velocities, lives, float(s.dist_max) - float(s.dist_min))
             n = int(rec.shape[0])
             if n == 0:
@@ -1114,7 +938,6 @@ class Camera:
     def _shade_box(self, want):
         """The traversed box of shade_rays: False / None none; True the camera's own (_trav_box: around cam.pos, sized for
         dist_max); or (origin, dims) -- world coordinates of cell (0, 0, 0), multiples of chunk_size, and cells per axis."""
-        torch = self._torch
         if want is None or want is False or want is True:
             return self._trav_box(bool(want))
         origin, dims = want
@@ -1125,13 +948,7 @@ class Camera:
                              "dims, not %r" % (want,))
         if dims[0] * dims[1] * dims[2] > (1 << 28):
             raise ValueError("shade_rays: the traversed box %r has more than 2**28 cells" % (dims,))
-        tr = nat.VrtTraversed()
-        keys = torch.empty((dims[0] * dims[1] * dims[2],), dtype=torch.int64, device=self._device)
-        tr.origin[:] = origin
-        tr.dims[:] = dims
-        tr.reset = 1
-        tr.d_keys = keys.data_ptr()
-        return tr, keys
+        return self._key_box(origin, dims)
 
     def shade_rays(self, origins, velocities=None, lives=None, *, seeds=None, draws=None, n_draws=None, max_life=None,
                    want_records=True, want_traversed=False, stream=None):
@@ -1158,11 +975,7 @@ class Camera:
         L = nat.lib()
         dev = self._require_device()
         s = self._settings()
-        if max_life is None:
-            max_life = float(s.dist_max)
-        max_life = float(max_life)
-        if not (max_life > 0) or max_life > float(1 << 28):
-            raise ValueError("shade_rays: max_life must lie in (0, 2**28], not %r" % max_life)
+        max_life = _max_life(max_life, s.dist_max, "shade_rays")
         if seeds is not None and draws is not None:
             raise ValueError("shade_rays: pass seeds or draws, not both")
         if seeds is not None:
@@ -1173,7 +986,7 @@ class Camera:
         st = self._c_settings(0)
         if not torch.cuda.is_current_stream_capturing():
             _ensure_pow_memo(torch, dev, s.falloff)
-        with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        with torch.cuda.device(dev), self._on_stream(stream):
             rec = self._cast_records(origins, velocities, lives, float(s.dist_max) - float(s.dist_min), "shade_rays")
             n = int(rec.shape[0])
             if n == 0:
@@ -1182,34 +995,11 @@ class Camera:
                 raise ValueError("shade_rays: 2**32 - 1 rays and more need several calls")
             cur = torch.cuda.current_stream().cuda_stream
             if seeds is not None:
-                if isinstance(seeds, torch.Tensor):
-                    if seeds.dtype.is_floating_point or seeds.dtype == torch.bool:
-                        raise ValueError("shade_rays: seeds must be integers, not %s" % seeds.dtype)
-                    sd = seeds.to(device=dev, dtype=torch.int64)
-                else:
-                    a = np.asarray(seeds)
-                    if a.dtype.kind not in "iu" or (a.size and (int(a.min()) < 0 or int(a.max()) >= 1 << 63)):
-                        raise ValueError("shade_rays: seeds must be integers in [0, 2**63)")
-                    sd = torch.from_numpy(np.array(a, np.int64)).to(dev)
-                if sd.dim() != 1 or int(sd.shape[0]) != n:
-                    raise ValueError("shade_rays: seeds must have shape [%d], not %s" % (n, list(sd.shape)))
-                sd = sd.contiguous()
+                sd = _seeds(seeds, n, "shade_rays", dev)
                 dd = torch.empty((n, n_draws), dtype=torch.float64, device=dev)
                 nat.check(L.vrt_rng_draws(sd.data_ptr(), n, n_draws, dd.data_ptr(), cur), "vrt_rng_draws")
             elif draws is not None:
-                if isinstance(draws, torch.Tensor):
-                    if not draws.dtype.is_floating_point:
-                        raise ValueError("shade_rays: draws must be floating point, not %s" % draws.dtype)
-                    dd = draws.to(device=dev, dtype=torch.float64)
-                else:
-                    a = np.asarray(draws)
-                    if a.dtype.kind not in "fiu":
-                        raise ValueError("shade_rays: draws must be numbers, not %s" % a.dtype)
-                    dd = torch.from_numpy(np.array(a, np.float64)).to(dev)
-                if dd.dim() != 2 or int(dd.shape[0]) != n or (n_draws is not None and int(dd.shape[1]) != int(n_draws)):
-                    raise ValueError("shade_rays: draws must have shape [%d, %s], not %s"
-                                     % (n, "n_draws" if n_draws is None else int(n_draws), list(dd.shape)))
-                dd = dd.contiguous()
+                dd = _floats(draws, "draws", "shade_rays", (n, "n_draws" if n_draws is None else int(n_draws)), dev).contiguous()
                 n_draws = int(dd.shape[1])
             else:
                 dd, n_draws = None, 0
@@ -1242,23 +1032,8 @@ class Camera:
         Raises ValueError when the cast rejected a pair (see cast_rays); that check synchronises."""
         torch = self._torch
         dev = self._require_device()
-
-        def pts(name, v):
-            if isinstance(v, torch.Tensor):
-                if not v.dtype.is_floating_point:
-                    raise ValueError("line_of_sight: %s must be floating point, not %s" % (name, v.dtype))
-                v = v.to(device=dev, dtype=torch.float64)
-            else:
-                arr = np.asarray(v)
-                if arr.dtype.kind not in "fiu":
-                    raise ValueError("line_of_sight: %s must be numbers, not %s" % (name, arr.dtype))
-                v = torch.from_numpy(np.array(arr, np.float64)).to(dev)
-            if v.dim() != 2 or v.shape[1] != 3:
-                raise ValueError("line_of_sight: %s must have shape [n, 3], not %s" % (name, list(v.shape)))
-            return v
-
-        with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
-            pa, pb = pts("a", a), pts("b", b)
+        with torch.cuda.device(dev), self._on_stream(stream):
+            pa, pb = (_floats(v, name, "line_of_sight", ("n", 3), dev) for name, v in (("a", a), ("b", b)))
             if pa.shape != pb.shape:
                 raise ValueError("line_of_sight: %d points a but %d points b" % (int(pa.shape[0]), int(pb.shape[0])))
             if int(pa.shape[0]) == 0:
@@ -1375,10 +1150,7 @@ class Camera:
                         vel=vec3(*[float(v) for v in r["vel"]]), step=float(r["step"]), life=float(r["life"]),
                         bounces=float(r["bounces"]), traversed=[])
             if n == 1:
-                rr = RenderResult()
-                rr.traversed_keys, rr.trav_origin, rr.trav_dims = keys, [int(v) for v in tr.origin], \
-                    [int(v) for v in tr.dims]
-                ray.traversed = rr.traversed(int(self._settings().chunk_size))
+                ray.traversed = _traversed_positions(keys, list(tr.origin), list(tr.dims), int(self._settings().chunk_size))
             out.append(ray)
         self.last_trace_records = rec
         return out

@@ -1,0 +1,178 @@
+"""What the Camera's calls return: device tensors (torch) plus a 16-word statistics block that reaches the host on request."""
+import numpy as np
+
+from . import _native as nat
+
+
+def _traversed_positions(keys, origin, dims, chunk_size):
+    """Visited chunk positions of a traversed box (include/vrt.h, vrt_traversed: `keys` one int64 per chunk cell, -1 never
+    visited; cell (0, 0, 0) is the chunk at `origin`) in the reference's order, which is the order of the keys: the
+    order-preserving union over rays in call order (reference init.py:72-73, 143; lib.py:404-409).  [] without keys."""
+    import torch
+    if keys is None:
+        return []
+    idx = torch.nonzero(keys != -1).flatten()
+    if idx.numel() == 0:
+        return []
+    idx = idx[torch.argsort(keys[idx])].cpu().numpy()
+    cz = idx % dims[2]
+    cy = (idx // dims[2]) % dims[1]
+    cx = idx // (dims[2] * dims[1])
+    return [(float(origin[0] + a * chunk_size), float(origin[1] + b * chunk_size), float(origin[2] + c * chunk_size))
+            for a, b, c in zip(cx.tolist(), cy.tolist(), cz.tolist())]
+
+
+class RenderResult:
+    """Device-side outputs of one tile render (torch tensors) plus host statistics."""
+
+    def __init__(self):
+        self.rgba_f32 = None     # [n_px, 4] float32: per-pixel mean of [r, g, b, alpha] (before Surface.set_at)
+        self.image_u8 = None     # [H, W, 4] uint8 full-window RGBA, non-owned pixels 0
+        self.ray_rgba = None     # [n_px * max_samples] int32 packed per-sample r|g<<8|b<<16|a<<24
+        self.rays = None         # numpy structured array of per-ray end states (only if requested)
+        self.stats = None        # numpy int64[16]
+        self.traversed_keys = None
+        self.trav_origin = None
+        self.trav_dims = None
+        self.max_samples = 1
+        self.pixels = None
+
+    def counters(self):
+        return {k: int(self.stats[i]) for i, k in enumerate(nat.COUNTER_NAMES)}
+
+    def traversed(self, chunk_size):
+        """Visited chunk positions in the reference's order (order-preserving union over rays in call order,
+        reference init.py:72-73, 143; lib.py:404-409)."""
+        return _traversed_positions(self.traversed_keys, self.trav_origin, self.trav_dims, chunk_size)
+
+
+class _LazyStats:
+    """`stats` of a call that does not synchronise: the device block `_stats_dev` (numpy int64[16] once read), copied to the
+    host on first use -- a synchronisation -- and kept.  What the words count is in each class's own docstring."""
+    _stats = None
+
+    @property
+    def stats(self):
+        if self._stats is None:
+            self._stats = self._stats_dev.cpu().numpy()
+        return self._stats
+
+
+class _HitRecords(_LazyStats):
+    """`step`, `pos`, `cell` and `material`: views of one buffer of 48-byte vrt_hit records (include/vrt.h)."""
+
+    def __init__(self, records, stats_dev):
+        import torch
+        n = records.numel() // nat.HIT_BYTES
+        f64 = records.view(torch.float64).view(n, nat.HIT_BYTES // 8)
+        i32 = records.view(torch.int32).view(n, nat.HIT_BYTES // 4)
+        self.records = records           # uint8 [n * 48]
+        self.step = f64[:, 0]            # float64 [n]: ray.step at the first voxel, or >= the ray's life for a miss
+        self.pos = f64[:, 1:4]           # float64 [n, 3]: ray.pos at that moment
+        self.cell = i32[:, 8:11]         # int32 [n, 3]: floor(pos)
+        self.material = i32[:, 11]       # int32 [n]: 1..255 the material found, 0 none; < 0: see the class
+        self._stats_dev = stats_dev
+
+    def numpy(self):
+        """The records as a numpy structured array (fields step, pos, cell, material)."""
+        return self.records.cpu().numpy().view(np.dtype(nat.HIT_FIELDS))
+
+
+class HitResult(_HitRecords):
+    """Device-side records of a first-hit pass (Camera.first_hit / first_hit_views): what every primary ray of the frame sees.
+    `step`, `pos`, `cell` and `material` are views of one buffer of 48-byte vrt_hit records (include/vrt.h), one per ray
+    slot p * max_samples + s (`samples` == max_samples) or one per pixel (`samples` == 1: every pixel's first sample);
+    material -1 marks an unused sample slot.
+    `stats`: numpy int64[16], copied from the device on first use (a synchronisation): word 8 = rays traced, word 4 = rays
+    that found a voxel.  A batch's views share one block: the batch's totals."""
+
+    def __init__(self, records, pixels, samples, max_samples, height, width, stats_dev):
+        super().__init__(records, stats_dev)
+        self.pixels = pixels             # numpy [n_px, 2] (x, y)
+        self.samples = samples
+        self.max_samples = max_samples
+        self.height, self.width = height, width
+
+    def _scatter(self, values, fill, dtype):
+        import torch
+        img = torch.full((self.height, self.width), fill, dtype=dtype, device=self.records.device)
+        px = torch.from_numpy(self.pixels.astype(np.int64)).to(self.records.device)
+        img[px[:, 1], px[:, 0]] = values[:: self.samples]
+        return img
+
+    def depth_image(self):
+        """[height, width] float64: sample 0's step where it found a voxel, inf where it found none and at pixels that
+        are not listed."""
+        import torch
+        inf = torch.full_like(self.step, float("inf"))
+        return self._scatter(torch.where(self.material > 0, self.step, inf), float("inf"), torch.float64)
+
+    def material_image(self):
+        """[height, width] int32: the material id sample 0 found (0: none); -1 at pixels that are not listed."""
+        import torch
+        return self._scatter(self.material, -1, torch.int32)
+
+
+class CastResult(_HitRecords):
+    """Device-side records of Camera.cast_rays: what every explicit ray found.  `step`, `pos`, `cell` and `material` are
+    views of one buffer of 48-byte vrt_hit records (include/vrt.h), record k for ray k; material -2: the ray was rejected.
+    `stats`: numpy int64[16], copied from the device on first use (a synchronisation): word 8 = rays marched, word 4 = rays
+    that found a voxel, word 9 = rays rejected."""
+
+    def hit_mask(self):
+        """torch.bool [n]: the ray found a voxel within its life."""
+        return self.material > 0
+
+    def rejected_mask(self):
+        """torch.bool [n]: the ray was rejected on the device (not finite, life > max_life, |vel| > 2**25, or out of
+        range: include/vrt.h, vrt_cast_ray) and was not marched."""
+        return self.material == nat.HIT_REJECTED
+
+
+class ShadeResult(_LazyStats):
+    """Device-side outputs of Camera.shade_rays: what colour and energy arrived along every explicit ray.  `rgba` is packed
+    r | g << 8 | b << 16 | alpha << 24, entry k for ray k; `records` (or None) one buffer of 152-byte vrt_ray records
+    (include/vrt.h), whose `s` field is 0 for a completed ray, -2 for a rejected one and -3 for one whose draws ran out.
+    `stats`: numpy int64[16], copied from the device on first use (a synchronisation): words 0..7 event sums over completed
+    rays, 8 completed rays, 9 rejected, 10 rays whose draws ran out, 11 chunk visits outside the traversed box."""
+
+    def __init__(self, rgba, records, stats_dev, trav=None):
+        self.rgba = rgba                 # uint32 [n]
+        self.records = records           # uint8 [n * 152], or None
+        self._stats_dev = stats_dev
+        self.traversed_keys, self.trav_origin, self.trav_dims = trav if trav is not None else (None, None, None)
+
+    def _s(self, what):
+        import torch
+        if self.records is None:
+            raise ValueError("%s needs the records (shade_rays(..., want_records=True))" % what)
+        n = self.records.numel() // nat.RAY_BYTES
+        return self.records.view(torch.int32).view(n, nat.RAY_BYTES // 4)[:, 2]
+
+    def numpy(self):
+        """The records as a numpy structured array of vrt_ray (fields x, y, s, color, alpha, ntrav, counters, detail,
+        energy, step, life, bounces, pos, vel)."""
+        if self.records is None:
+            raise ValueError("numpy() needs the records (shade_rays(..., want_records=True))")
+        return self.records.cpu().numpy().view(np.dtype(nat.RAY_FIELDS, align=True))
+
+    def rejected_mask(self):
+        """torch.bool [n]: the ray was rejected on the device (cast_rays's rule) and was not marched."""
+        return self._s("rejected_mask()") == nat.RAY_REJECTED
+
+    def exhausted_mask(self):
+        """torch.bool [n]: the ray needed more draws than it was given and was not completed: repeat it with a longer row."""
+        return self._s("exhausted_mask()") == nat.RAY_EXHAUSTED
+
+    def image(self, height, width):
+        """[height, width, 4] uint8 RGBA from n == height * width rays in row-major order (ray y * width + x is pixel (x, y))."""
+        import torch
+        height, width = int(height), int(width)
+        if height <= 0 or width <= 0 or height * width != int(self.rgba.numel()):
+            raise ValueError("image(%d, %d): %d rays are not %d x %d pixels" % (height, width, int(self.rgba.numel()), height, width))
+        return self.rgba.view(torch.uint8).view(height, width, 4)
+
+    def traversed(self, chunk_size):
+        """Visited chunk positions inside the box the call was given, in the reference's order (the order-preserving union
+        over the rays in array order); [] without a box."""
+        return _traversed_positions(self.traversed_keys, self.trav_origin, self.trav_dims, chunk_size)

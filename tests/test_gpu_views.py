@@ -160,6 +160,28 @@ def test_one_view_equals_render():
 
 
 @gpu
+def test_batch_calls_share_the_pose_records_and_leave_the_camera_alone():
+    """16 x 9 x 1, an unrotated and a rotated pose: first_hit_views and render_views of the same poses use one device copy of
+    the records; the boxes are sized from the poses' rotations, not by moving the camera; every view's box has the largest
+    dimensions of the batch."""
+    st = settings(width=16, height=9, samples=1)
+    poses = POSES[:2]
+    cam = camera_for(scene(2), settings_store(st), *POSES[2], lens_of(st))
+    pos, rot = cam.pos, cam.rot
+    assert len(cam.first_hit_views(poses)) == 2
+    cams = cam._views_cams[1]
+    ptr = cams.data_ptr()
+    got = cam.render_views(poses, want_traversed=True)
+    assert cam._views_cams[1] is cams and cams.data_ptr() == ptr
+    assert cam.pos is pos and cam.rot is rot
+    n = [2 * cam._box_radius(q) + 1 for _, q in poses]
+    assert n[1] > n[0]
+    for r in got:
+        assert r.trav_dims == [n[1]] * 3 and r.traversed_keys.numel() == n[1] ** 3
+    assert got[0].trav_origin != got[1].trav_origin
+
+
+@gpu
 def test_batch_with_one_ray_record_per_pixel():
     """dof, lod_random and lod_samples all 0: the ray table holds one record per PIXEL, and a ray's first-hit draws come from
     the draw table (the other layout of take_ray_views)."""
