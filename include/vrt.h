@@ -460,6 +460,43 @@ int vrt_voxelize(const vrt_object* d_objects, int32_t n_objects, const uint8_t* 
                  const int64_t* origin, const int32_t* dims, int32_t chunk_size, const uint32_t* d_chunk_list,
                  int64_t n_list, uint32_t* d_world_table, uint8_t* d_voxels, void* stream);
 
+/* ---- sprite edits on the resident models ----------------------------------------------------------------
+ * Sprite.set_voxel / set_voxels_area / clear (data.py:382-427) as operation records applied to d_models in place, so that
+ * an edit costs a few bytes of upload and a vrt_voxelize of the chunks it can change, not a re-upload of the model. */
+typedef struct vrt_edit {      /* 64 bytes, 16-byte aligned */
+    int64_t model;             /* offset of the target model in d_models */
+    int32_t size[3];           /* its shape [size.x][size.y][size.z] */
+    int32_t lo[3], hi[3];      /* inclusive box, 0 <= lo <= hi < size (a point is a box of one voxel) */
+    int32_t value;             /* local material id 1..255, 0 clears */
+    int32_t force;             /* 0: only where the model byte is 0 */
+    int32_t pad[3];
+} vrt_edit;
+/* The word vrt_edit_models writes into d_stats (every other word 0). */
+enum { VRT_S_EDIT_INVALID = 9   /* records the device refused: none of their voxels was written */ };
+
+/* After the call d_models equals the result of applying the n_edits records of d_edits (a DEVICE array, 16-byte aligned)
+ * one after another in array order: a later record wins, and a record with force = 0 sees what the earlier ones left.
+ * One launch serves all records (up to 65535; more are split), without atomics on the models: a thread owns one voxel of the
+ * bounding box of the records that target its model, replays in order the records that cover it and writes once, and only
+ * if the byte changed.  Records target the same model when `model` and `size` agree; records of DIFFERENT models whose
+ * byte ranges overlap are applied in no defined order (every write still lies inside a validated model).
+ * The device validates every record: size >= 1, lo <= hi inside size, model >= 0, model + size.x * size.y * size.z <=
+ * models_bytes, 0 <= value <= 255.  An invalid record is skipped as a whole, never partly applied, and counted in
+ * d_stats[VRT_S_EDIT_INVALID]; no byte outside [d_models, d_models + models_bytes) is ever read or written.
+ *   d_stats   [VRT_NSTATS] uint64, zeroed by the callee.
+ * n_edits = 0 only zeroes the statistics.  Every host-visible argument is checked before any HIP call; nothing is allocated
+ * or synchronised, so a call may be captured into a hipGraph. */
+int vrt_edit_models(uint8_t* d_models, int64_t models_bytes, const vrt_edit* d_edits, int32_t n_edits,
+                    uint64_t* d_stats, void* stream);
+
+/* Sprite.mix (data.py:311-321) for one frame pair: with i over the size.x * size.y * size.z bytes of two models of the same
+ * shape at offsets dst and src of d_models,  dst[i] = d_idmap[src[i]]  where src[i] != 0 and (force or dst[i] == 0).
+ *   d_idmap   256 bytes on the device: the source model's local material ids -> the target's (entry 0 unused).
+ * VRT_ERR_ARG: a model that leaves [0, models_bytes), or dst and src ranges that overlap.  Checked before any HIP call;
+ * nothing is allocated or synchronised. */
+int vrt_stamp_model(uint8_t* d_models, int64_t models_bytes, int64_t dst, int64_t src, const int32_t* size,
+                    const uint8_t* d_idmap, int32_t force, void* stream);
+
 /* ---- owners of hit records -----------------------------------------------------------------------------
  * Which OBJECT a hit belongs to, and which voxel of that object's model: what picking, instance images and sprite edits
  * act on.  vrt_voxelize keeps only the material byte ("the later object wins"); the owner pass asks voxelize's question

@@ -124,6 +124,18 @@ OWNER_FIELDS = [("object", "<i4"), ("resolution", "<i4"), ("voxel", "<i4", 3), (
 OWNER_BYTES = 32
 OWNER_NONE, OWNER_ORPHAN = -1, -2   # vrt_owner.object of a record that is no hit / that no object accounts for
 
+
+class VrtEdit(C.Structure):
+    """vrt_edit (include/vrt.h): one box of a model set to a local material id (0 clears), 64 bytes."""
+    _fields_ = [("model", C.c_int64), ("size", C.c_int32 * 3), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3),
+                ("value", C.c_int32), ("force", C.c_int32), ("pad", C.c_int32 * 3)]
+
+
+EDIT_FIELDS = [("model", "<i8"), ("size", "<i4", 3), ("lo", "<i4", 3), ("hi", "<i4", 3), ("value", "<i4"), ("force", "<i4"),
+               ("pad", "<i4", 3)]
+EDIT_BYTES = 64
+S_EDIT_INVALID = 9   # vrt_edit_models only (VRT_S_EDIT_INVALID): records the device refused
+
 _lib = None
 
 
@@ -213,6 +225,10 @@ def lib():
     L.vrt_voxelize.argtypes = [vp, i32, vp, vp, C.POINTER(i64), C.POINTER(i32), i32, vp, i64, vp, vp, vp]
     L.vrt_hit_owners.restype = C.c_int
     L.vrt_hit_owners.argtypes = [C.POINTER(VrtScene), vp, i64, vp, i32, vp, vp, vp, vp, vp]
+    L.vrt_edit_models.restype = C.c_int
+    L.vrt_edit_models.argtypes = [vp, i64, vp, i32, vp, vp]
+    L.vrt_stamp_model.restype = C.c_int
+    L.vrt_stamp_model.argtypes = [vp, i64, i64, i64, C.POINTER(i32), vp, i32, vp]
     L.vrt_canvas_blit.restype = C.c_int
     L.vrt_canvas_blit.argtypes = [vp, vp, i32, i32, vp, i64, vp]
     L.vrt_profile_begin.restype = C.c_int
@@ -244,7 +260,7 @@ EXPORTS = ["vrt_abi_version", "vrt_status_string", "vrt_last_hip_error", "vrt_de
            "vrt_pow_memo_create", "vrt_occupancy_build", "vrt_canvas_blit", "vrt_world_tables_bytes", "vrt_world_tables_build",
            "vrt_trace_workspace_bytes", "vrt_trace_rays", "vrt_rng_draws",
            "vrt_synth_volume", "vrt_profile_begin", "vrt_profile_begin_kinds", "vrt_profile_end", "vrt_select_chunks", "vrt_voxelize",
-           "vrt_hit_owners"]
+           "vrt_hit_owners", "vrt_edit_models", "vrt_stamp_model"]
 
 
 PLAN_FIELDS = ("launches", "pool", "wt_on", "trav_words", "bm_window", "ct_cells", "n_materials", "dyn_bytes", "static_bytes")

@@ -3978,6 +3978,79 @@ __global__ void __launch_bounds__(VRT_BLOCK) voxelize_kernel(const vrt_object* o
 }
 
 // ---------------------------------------------------------------------------------------------
+// sprite edits (vrt_edit_models, vrt_stamp_model): Sprite.set_voxel / set_voxels_area / clear / mix on the resident models
+// ---------------------------------------------------------------------------------------------
+#define VRT_EDIT_TILES 64   // workgroups that share one model's bounding box (blockIdx.x)
+
+// the record can be applied as a whole: a box inside its model, the model inside the buffer, a value that fits a byte
+__device__ __forceinline__ bool edit_valid(const vrt_edit& e, int64_t models_bytes) {
+    if (e.size[0] < 1 || e.size[1] < 1 || e.size[2] < 1 || e.model < 0) return false;
+    // (each extent is below 2^31, so the first product cannot wrap; the second is compared by division)
+    const int64_t xy = (int64_t)e.size[0] * e.size[1];
+    if (xy > models_bytes / e.size[2] || e.model > models_bytes - xy * e.size[2]) return false;
+    for (int a = 0; a < 3; a++)
+        if (e.lo[a] < 0 || e.lo[a] > e.hi[a] || e.hi[a] >= e.size[a]) return false;
+    return e.value >= 0 && e.value <= 255;
+}
+__device__ __forceinline__ bool edit_same_model(const vrt_edit& a, const vrt_edit& b) {
+    return a.model == b.model && a.size[0] == b.size[0] && a.size[1] == b.size[1] && a.size[2] == b.size[2];
+}
+
+// blockIdx.y = a record.  The row of the FIRST valid record of a model works for all of that model's records and every
+// other row leaves at once, so no two threads ever own the same byte: a thread takes one voxel of the bounding box of the
+// model's records (lanes along z, the model's innermost axis), replays the records that cover it in array order and writes
+// once, if the byte changed.  The record index is the same in every lane: the records come through uniform loads.
+__global__ void __launch_bounds__(VRT_BLOCK) edit_models_kernel(uint8_t* __restrict__ models, int64_t models_bytes,
+                                                                const vrt_edit* __restrict__ edits, int first, int n_edits,
+                                                                unsigned long long* __restrict__ stats) {
+    const int r = first + (int)blockIdx.y;
+    const vrt_edit& lead = edits[r];
+    if (!edit_valid(lead, models_bytes)) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&stats[VRT_S_EDIT_INVALID], 1ull);
+        return;
+    }
+    for (int k = 0; k < r; k++) {
+        const vrt_edit& e = edits[k];
+        if (edit_same_model(e, lead) && edit_valid(e, models_bytes)) return;  // (an earlier row leads this model)
+    }
+    int lo0 = lead.lo[0], lo1 = lead.lo[1], lo2 = lead.lo[2], hi0 = lead.hi[0], hi1 = lead.hi[1], hi2 = lead.hi[2];
+    for (int k = r + 1; k < n_edits; k++) {
+        const vrt_edit& e = edits[k];
+        if (!edit_same_model(e, lead) || !edit_valid(e, models_bytes)) continue;
+        lo0 = min(lo0, e.lo[0]), lo1 = min(lo1, e.lo[1]), lo2 = min(lo2, e.lo[2]);
+        hi0 = max(hi0, e.hi[0]), hi1 = max(hi1, e.hi[1]), hi2 = max(hi2, e.hi[2]);
+    }
+    const int d1 = hi1 - lo1 + 1, d2 = hi2 - lo2 + 1;
+    const int64_t count = (int64_t)(hi0 - lo0 + 1) * d1 * d2;
+    const int sy = lead.size[1], sz = lead.size[2];
+    uint8_t* model = models + lead.model;
+    for (int64_t i = (int64_t)blockIdx.x * VRT_BLOCK + threadIdx.x; i < count; i += (int64_t)VRT_EDIT_TILES * VRT_BLOCK) {
+        const int z = lo2 + (int)(i % d2), y = lo1 + (int)((i / d2) % d1), x = lo0 + (int)(i / ((int64_t)d1 * d2));
+        uint8_t* at = model + ((int64_t)x * sy + y) * sz + z;
+        const int before = *at;
+        int now = before;
+        for (int k = r; k < n_edits; k++) {
+            const vrt_edit& e = edits[k];
+            if (!edit_same_model(e, lead) || !edit_valid(e, models_bytes)) continue;
+            if (x < e.lo[0] || y < e.lo[1] || z < e.lo[2] || x > e.hi[0] || y > e.hi[1] || z > e.hi[2]) continue;
+            if (e.force || now == 0) now = e.value;
+        }
+        if (now != before) *at = (uint8_t)now;
+    }
+}
+
+// Sprite.mix for one frame pair: the source's voxels, renumbered through `idmap`, over the target's (force) or into its gaps
+__global__ void __launch_bounds__(VRT_BLOCK) stamp_model_kernel(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src,
+                                                                const uint8_t* __restrict__ idmap, int64_t n, int force) {
+    for (int64_t i = (int64_t)blockIdx.x * VRT_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * VRT_BLOCK) {
+        const int s = src[i];
+        if (!s) continue;
+        const int d = dst[i], v = idmap[s];
+        if ((force || d == 0) && v != d) dst[i] = (uint8_t)v;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // owner pass (vrt_hit_owners): which object, and which voxel of its model, a hit record belongs to
 // ---------------------------------------------------------------------------------------------
 struct OwnerParams {
@@ -6038,6 +6111,40 @@ int vrt_voxelize(const vrt_object* d_objects, int32_t n_objects, const uint8_t* 
     hipLaunchKernelGGL(voxelize_kernel, dim3((unsigned)blocks), dim3(VRT_BLOCK), 0, stream, d_objects, (int)n_objects, d_models,
                        d_remap, (int)origin[0], (int)origin[1], (int)origin[2], (int)dims[1], (int)dims[2], (int)cs,
                        d_chunk_list, d_world_table, d_voxels);
+    HIP_TRY(hipGetLastError());
+    return VRT_OK;
+}
+
+int vrt_edit_models(uint8_t* d_models, int64_t models_bytes, const vrt_edit* d_edits, int32_t n_edits, uint64_t* d_stats,
+                    void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    // (every check comes before any HIP call)
+    if (!d_stats || n_edits < 0 || models_bytes < 0) return VRT_ERR_ARG;
+    if (n_edits > 0 && (!d_models || !d_edits || ((uintptr_t)d_edits & 15) != 0)) return VRT_ERR_ARG;
+    frame_begin(d_stats, nullptr, 0, nullptr, 0, nullptr, stream);
+    // (a grid has at most 65535 rows; the row that leads a model replays ALL of its records, those of later launches too)
+    for (int32_t first = 0; first < n_edits; first += 65535) {
+        const int rows = n_edits - first < 65535 ? n_edits - first : 65535;
+        hipLaunchKernelGGL(edit_models_kernel, dim3(VRT_EDIT_TILES, (unsigned)rows), dim3(VRT_BLOCK), 0, stream, d_models, models_bytes,
+                           d_edits, (int)first, (int)n_edits, (unsigned long long*)d_stats);
+    }
+    HIP_TRY(hipGetLastError());
+    return VRT_OK;
+}
+
+int vrt_stamp_model(uint8_t* d_models, int64_t models_bytes, int64_t dst, int64_t src, const int32_t* size, const uint8_t* d_idmap,
+                    int32_t force, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!d_models || !size || !d_idmap || models_bytes < 0 || dst < 0 || src < 0) return VRT_ERR_ARG;
+    if (size[0] < 1 || size[1] < 1 || size[2] < 1) return VRT_ERR_ARG;
+    const int64_t xy = (int64_t)size[0] * size[1];
+    if (xy > models_bytes / size[2]) return VRT_ERR_ARG;
+    const int64_t n = xy * size[2];
+    if (dst > models_bytes - n || src > models_bytes - n) return VRT_ERR_ARG;
+    if (dst < src + n && src < dst + n) return VRT_ERR_ARG;  // (the two models overlap)
+    const int64_t blocks = (n + VRT_BLOCK - 1) / VRT_BLOCK;
+    hipLaunchKernelGGL(stamp_model_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(VRT_BLOCK), 0, stream, d_models + dst,
+                       d_models + src, d_idmap, n, (int)force);
     HIP_TRY(hipGetLastError());
     return VRT_OK;
 }
