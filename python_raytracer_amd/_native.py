@@ -244,6 +244,9 @@ def lib():
     # diagnostic, not part of include/vrt.h: which march instance a launch with the given inputs runs (march_variant below)
     L.vrt_diag_march_variant.restype = C.c_int
     L.vrt_diag_march_variant.argtypes = [C.POINTER(i32), C.c_int, C.c_char_p, C.c_int, C.POINTER(i32)]
+    # diagnostic, not part of include/vrt.h: how often this process has launched each kernel instance (launch_census below)
+    L.vrt_diag_launch_census.restype = C.c_int
+    L.vrt_diag_launch_census.argtypes = [C.c_int, C.c_char_p, C.c_int, C.POINTER(i64)]
     if L.vrt_abi_version() != ABI_VERSION:
         raise ImportError("python_raytracer_amd/_vrt.so has ABI version %d, expected %d"
                           % (L.vrt_abi_version(), ABI_VERSION))
@@ -300,6 +303,22 @@ def march_variant(**inputs):
     name, effects = C.create_string_buffer(128), (C.c_int32 * 3)()
     status = lib().vrt_diag_march_variant(words, len(VARIANT_INPUTS), name, len(name), effects)
     return (status, name.value.decode(), tuple(effects)) if status == 0 else (status, None, None)
+
+
+def launch_census():
+    """vrt_diag_launch_census as {instance name with every template argument: launches since the process started}: the rows
+    of the march table (launch_march: frames, records, re-traces), then the instances of the families chosen by resolution
+    mode (batched views and their re-traces, first hit, cast, shade).  Host memory only: needs no GPU, synchronises nothing."""
+    L = lib()
+    name, count = C.create_string_buffer(128), C.c_int64(0)
+    census, row, n = {}, 0, 1
+    while row < n:
+        n = L.vrt_diag_launch_census(row, name, len(name), C.byref(count))
+        if n < 0:
+            check(n, "vrt_diag_launch_census")
+        census[name.value.decode()] = int(count.value)
+        row += 1
+    return census
 
 
 def check(status, what):

@@ -27,6 +27,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <mutex>
 #include <vector>
 
@@ -5134,6 +5135,10 @@ struct MarchInstance { MarchVariant v; MarchFn fn; const char* name; };
 #define VRT_ROW(POOL, ...) {{POOL, __VA_ARGS__}, &VRT_FN_##POOL(__VA_ARGS__), VRT_STR(VRT_FN_##POOL(__VA_ARGS__))},
 static const MarchInstance g_march_instances[] = {VRT_MARCH_INSTANCES(VRT_ROW)};
 #undef VRT_ROW
+#define VRT_N_MARCH_INSTANCES ((int)(sizeof g_march_instances / sizeof g_march_instances[0]))
+// The launch census (vrt_diag_launch_census): how often launch_march has launched each row of the table since the process
+// started.  Host memory only, bumped next to the launch; a diagnostic for the tests that name the instance they mean to run.
+static std::atomic<int64_t> g_march_launches[VRT_N_MARCH_INSTANCES];
 
 // the 8-position kernels of the byte lookup -- look-ahead (W), late key comparison (DEFER), no ray table (PERPIX 3) -- exist
 // for this launch: resolutions <= 2, the deep speculation compiled as 8 positions
@@ -5196,6 +5201,33 @@ static inline void launch_fn(MarchFn fn, int grid, size_t lds, hipStream_t strea
 // the kernels that come as three instances (batched views, first hit, explicit rays): VRT_SPEC_DEEP positions per step for
 // resolutions <= 2, VRT_SPEC for the generic instance, like the frame's march of scenes that fit the caches; K(SPEC, RESMODE): the instance
 #define VRT_BY_RES(resmode, K) ((resmode) == 0 ? (MarchFn)K(VRT_SPEC_DEEP, 0) : (resmode) == 1 ? (MarchFn)K(VRT_SPEC_DEEP, 1) : (MarchFn)K(VRT_SPEC, 2))
+// ... and the census of those families: every instance a VRT_BY_RES site can launch (and the two re-trace instances of the
+// batched views), by its full name, with its launches since the process started (launch_by_res)
+struct ByResInstance { MarchFn fn; const char* name; };
+#define VRT_CENSUS_ROW(...) {(MarchFn)&__VA_ARGS__, VRT_STR(__VA_ARGS__)},
+#define VRT_CENSUS_BY_RES(K, ...) VRT_CENSUS_ROW(K<VRT_SPEC_DEEP,0,__VA_ARGS__>) VRT_CENSUS_ROW(K<VRT_SPEC_DEEP,1,__VA_ARGS__>) VRT_CENSUS_ROW(K<VRT_SPEC,2,__VA_ARGS__>)
+#define VRT_CENSUS_FIRST_HIT(S, R, V) VRT_CENSUS_ROW(first_hit_kernel<S,R,1,V>) VRT_CENSUS_ROW(first_hit_kernel<S,R,0,V>)
+#define VRT_CENSUS_FIRST_HITS(V) VRT_CENSUS_FIRST_HIT(VRT_SPEC_DEEP, 0, V) VRT_CENSUS_FIRST_HIT(VRT_SPEC_DEEP, 1, V) VRT_CENSUS_FIRST_HIT(VRT_SPEC, 2, V)
+// (the rows stand in the order in which the launch sites below name the instances: the compiler emits the kernels in the
+// order it first meets them, and an instance's code is not quite independent of its place in that order)
+static const ByResInstance g_by_res_instances[] = {
+    VRT_CENSUS_BY_RES(march_views_kernel, false,0)
+    VRT_CENSUS_ROW(march_views_kernel<VRT_SPEC,2,true,1>) VRT_CENSUS_ROW(march_views_kernel<VRT_SPEC,2,true,2>)
+    VRT_CENSUS_FIRST_HITS(false) VRT_CENSUS_FIRST_HITS(true)
+    VRT_CENSUS_ROW(cast_kernel<VRT_SPEC_DEEP,0>) VRT_CENSUS_ROW(cast_kernel<VRT_SPEC_DEEP,1>) VRT_CENSUS_ROW(cast_kernel<VRT_SPEC,2>)
+    VRT_CENSUS_BY_RES(shade_kernel, true) VRT_CENSUS_BY_RES(shade_kernel, false)};
+#undef VRT_CENSUS_FIRST_HITS
+#undef VRT_CENSUS_FIRST_HIT
+#undef VRT_CENSUS_BY_RES
+#undef VRT_CENSUS_ROW
+#define VRT_N_BY_RES_INSTANCES ((int)(sizeof g_by_res_instances / sizeof g_by_res_instances[0]))
+static std::atomic<int64_t> g_by_res_launches[VRT_N_BY_RES_INSTANCES];
+// launch_fn for those sites: counts the instance, then launches it
+static inline void launch_by_res(MarchFn fn, int grid, size_t lds, hipStream_t stream, const MarchParams& P) {
+    for (int i = 0; i < VRT_N_BY_RES_INSTANCES; i++)
+        if (g_by_res_instances[i].fn == fn) g_by_res_launches[i].fetch_add(1, std::memory_order_relaxed);
+    launch_fn(fn, grid, lds, stream, P);
+}
 // kernel variant: resolution mode from vrt_scene.max_resolution, speculation depth from the scene size (march_choose)
 static int launch_march(MarchParams P, int grid, int resmode, bool deep, bool pool, bool record, bool list, hipStream_t stream) {
     const bool big_scene = big_voxels(P.vox_bytes);
@@ -5209,6 +5241,7 @@ static int launch_march(MarchParams P, int grid, int resmode, bool deep, bool po
     if (pool) pool_policy(P, big_scene);
     const size_t lds = march_lds(P, c.k->v.lk == 2, pool);
     if (!list) plan_record(P, lds, pool);
+    g_march_launches[c.k - g_march_instances].fetch_add(1, std::memory_order_relaxed);
     launch_fn(c.k->fn, grid, lds, stream, P);
     return VRT_OK;
 }
@@ -5367,7 +5400,7 @@ static void launch_march_views(MarchParams P, int grid, int resmode, bool list, 
 #undef VRT_VIEWS
     if (list)  // one generic variant, like march_kernel's re-traces
         fn = P.list_seed == 1 ? &march_views_kernel<VRT_SPEC, 2, true, 1> : &march_views_kernel<VRT_SPEC, 2, true, 2>;
-    launch_fn(fn, grid, lds, stream, P);
+    launch_by_res(fn, grid, lds, stream, P);
 }
 
 extern "C" {
@@ -5698,7 +5731,7 @@ template <bool VIEWS>
 static void launch_first_hit(MarchParams P, int grid, int resmode, int64_t n_views, hipStream_t stream) {
     const size_t lds = first_hit_lds(P, VIEWS ? n_views : 0);
 #define VRT_FIRST_HIT(S, R) (P.per_pixel ? &first_hit_kernel<S, R, 1, VIEWS> : &first_hit_kernel<S, R, 0, VIEWS>)
-    launch_fn(VRT_BY_RES(resmode, VRT_FIRST_HIT), grid, lds, stream, P);
+    launch_by_res(VRT_BY_RES(resmode, VRT_FIRST_HIT), grid, lds, stream, P);
 #undef VRT_FIRST_HIT
 }
 // what both entry points check and set after fill_params: the pass reads no plan, draw table, materials or keys
@@ -5818,7 +5851,7 @@ int vrt_first_hit_views(const vrt_scene* scene, const vrt_settings* st, const vr
 static void launch_cast(MarchParams P, int grid, int resmode, hipStream_t stream) {
     const size_t lds = first_hit_lds(P, 0);  // the chunk table, if it fits
 #define VRT_CAST(S, R) &cast_kernel<S, R>
-    launch_fn(VRT_BY_RES(resmode, VRT_CAST), grid, lds, stream, P);
+    launch_by_res(VRT_BY_RES(resmode, VRT_CAST), grid, lds, stream, P);
 #undef VRT_CAST
 }
 
@@ -5830,7 +5863,7 @@ static void launch_shade(MarchParams P, int grid, int resmode, hipStream_t strea
     P.wt_on = 0;
     const size_t lds = march_lds(P, false, false);
 #define VRT_SHADE(S, R) &shade_kernel<S, R, RECORD>
-    launch_fn(VRT_BY_RES(resmode, VRT_SHADE), grid, lds, stream, P);
+    launch_by_res(VRT_BY_RES(resmode, VRT_SHADE), grid, lds, stream, P);
 #undef VRT_SHADE
 }
 
@@ -6046,6 +6079,22 @@ int vrt_diag_march_variant(const int32_t* in, int n_in, char* name, int name_cap
     effects[1] = c.trav_words;
     effects[2] = ci.tile_heads && c.keep_tile_heads;
     return VRT_OK;
+}
+
+// Diagnostic, outside include/vrt.h: the launch census.  Row `row` of it -- the rows of the march table (VRT_MARCH_INSTANCES) in
+// their order, then the instances of the families chosen by resolution mode (g_by_res_instances) -- as the instance's name
+// with every template argument in name[name_cap] and, in *count, how often this process has launched it so far.  Returns the
+// number of rows; VRT_ERR_ARG, with nothing written, for a row that does not exist, a null pointer or a name that does not
+// fit.  Host memory only: no device call, no synchronisation, legal during stream capture.
+int vrt_diag_launch_census(int row, char* name, int name_cap, int64_t* count) {
+    const int n = VRT_N_MARCH_INSTANCES + VRT_N_BY_RES_INSTANCES;
+    if (row < 0 || row >= n || !name || !count || name_cap < 1) return VRT_ERR_ARG;
+    const bool m = row < VRT_N_MARCH_INSTANCES;
+    const char* s = m ? g_march_instances[row].name : g_by_res_instances[row - VRT_N_MARCH_INSTANCES].name;
+    if ((size_t)name_cap <= strlen(s)) return VRT_ERR_ARG;
+    strcpy(name, s);
+    *count = (m ? g_march_launches[row] : g_by_res_launches[row - VRT_N_MARCH_INSTANCES]).load(std::memory_order_relaxed);
+    return n;
 }
 
 #ifdef VRT_DIAG

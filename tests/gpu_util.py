@@ -87,6 +87,31 @@ def march_dyn_lds(n_materials, ct_cells, bitmap_words, wt_cells, pool):
     return n + (POOL_LDS if pool else 0) + 16
 
 
+def frame_equals_oracle(r, o, cs):
+    """A frame rendered with want_ray_rgba against the oracle's (oracle_lib.render with its rays): fp32 means, event counters,
+    the traversed list in the reference's order and every sample's packed colour."""
+    assert np.array_equal(r.rgba_f32.cpu().numpy(), o["pix_mean"].astype(np.float32))
+    assert (r.stats[:8] == o["counters"]).all(), (r.stats[:8], o["counters"])
+    assert np.array_equal(np.array(r.traversed(cs), np.int64).reshape(-1, 3), np.asarray(o["traversed"]).reshape(-1, 3))
+    rays = o["rays"]
+    where = {(int(x), int(y)): i for i, (x, y) in enumerate(r.pixels)}
+    slot = np.array([where[(int(x), int(y))] for x, y in zip(rays["x"], rays["y"])], np.int64) * r.max_samples + rays["s"]
+    packed = (rays["color"][:, 0].astype(np.uint32) | (rays["color"][:, 1].astype(np.uint32) << 8) |
+              (rays["color"][:, 2].astype(np.uint32) << 16) | (rays["alpha"].astype(np.uint32) << 24))
+    got = r.ray_rgba.cpu().numpy().view(np.uint32)
+    assert np.array_equal(got[slot], packed)
+
+
+def launches_of(call):
+    """(call(), the kernel instances it launched): the names, with every template argument, whose count in the library's
+    launch census (_native.launch_census: host-side counters next to the launches) rose across the call."""
+    from python_raytracer_amd import _native as nat
+    before = nat.launch_census()
+    out = call()
+    after = nat.launch_census()
+    return out, {name for name in after if after[name] > before[name]}
+
+
 def check_frame_march(cam, o, cs, which, lookahead=None, window=None, expect_pool=None, **kw):
     """The same frame WITHOUT ray records: `want_rays` selects the recording march_kernel whatever VRT_POOL says, so this is
     the render that runs the frame kernel the fixture names -- march_pool_kernel under "pool" (asserted: its workgroups
@@ -106,16 +131,7 @@ def check_frame_march(cam, o, cs, which, lookahead=None, window=None, expect_poo
     assert (groups > 0) if expect_pool else (groups == 0), (which, groups)
     if lookahead is not None:   # did the march step look ahead across chunk borders (march_step_w)?
         assert (int(r.stats[14]) > 0) == bool(lookahead), (lookahead, int(r.stats[14]))
-    assert np.array_equal(r.rgba_f32.cpu().numpy(), o["pix_mean"].astype(np.float32))
-    assert (r.stats[:8] == o["counters"]).all(), (r.stats[:8], o["counters"])
-    assert np.array_equal(np.array(r.traversed(cs), np.int64).reshape(-1, 3), np.asarray(o["traversed"]).reshape(-1, 3))
-    rays = o["rays"]
-    where = {(int(x), int(y)): i for i, (x, y) in enumerate(r.pixels)}
-    slot = np.array([where[(int(x), int(y))] for x, y in zip(rays["x"], rays["y"])], np.int64) * r.max_samples + rays["s"]
-    packed = (rays["color"][:, 0].astype(np.uint32) | (rays["color"][:, 1].astype(np.uint32) << 8) |
-              (rays["color"][:, 2].astype(np.uint32) << 16) | (rays["alpha"].astype(np.uint32) << 24))
-    got = r.ray_rgba.cpu().numpy().view(np.uint32)
-    assert np.array_equal(got[slot], packed)
+    frame_equals_oracle(r, o, cs)
     # ... and once more without the settled-cell bitmap (VRT_TRAV_LDS=0, read at every launch): what traversed boxes too large
     # for one get -- every visit reads its cell's key, and the kernel instances that compare it after the voxel reads run
     # -- and, where the window's geometry allows (the pool kernel, a power-of-two run of pixels per hand-out that divides the

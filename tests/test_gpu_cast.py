@@ -10,7 +10,7 @@ import pytest
 
 import cast_ref as cr
 import oracle_lib as ol
-from gpu_util import HANDOUT_KNOBS, camera_for, run_children, settings_store
+from gpu_util import HANDOUT_KNOBS, camera_for, launches_of, run_children, settings_store
 from python_raytracer_amd import _native as nat
 
 gpu = pytest.mark.gpu
@@ -18,6 +18,9 @@ gpu = pytest.mark.gpu
 IDENTITY = (0.0, 0.0, 0.0, 1.0)
 HIT_DTYPE = cr.HIT_DTYPE
 _cams = {}
+# the instance a cast runs, by the highest resolution of the scene's chunks: what the launch census must show for a cast_rays call
+CAST_INSTANCE = {1: 'cast_kernel<8,0>', 2: 'cast_kernel<8,1>', 3: 'cast_kernel<4,2>'}
+RES_MAX = {"default": 2, "synth64": 1, "default_scaled": 2, "default_dmin": 2, "hand": 3, "big_table": 1}
 
 
 def scene_of(name):
@@ -44,7 +47,9 @@ def check_stats(stats, exp):
 def check_set(name):
     cam, _ = cam_of(name)
     sc, origins, vels, lives, exp = cr.ray_set(name)
-    res = cam.cast_rays(origins, vels, lives)
+    res, ran = launches_of(lambda: cam.cast_rays(origins, vels, lives))
+    assert ran == {CAST_INSTANCE[RES_MAX[name]]}, (name, ran)   # the instance the set is there for, and no other
+    assert int(cam._c_scene(cam._ensure_scene()).max_resolution) == RES_MAX[name]
     cr.assert_records_equal(res.numpy(), exp)
     check_stats(res.stats, exp)
     assert np.array_equal(res.hit_mask().cpu().numpy(), exp["material"] > 0) and not res.rejected_mask().any()

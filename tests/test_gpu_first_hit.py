@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
-from gpu_util import HANDOUT_KNOBS, camera_for, run_children, settings_store
+from gpu_util import HANDOUT_KNOBS, camera_for, launches_of, run_children, settings_store
 from python_raytracer_amd import _native as nat
 
 gpu = pytest.mark.gpu
@@ -23,6 +23,14 @@ gpu = pytest.mark.gpu
 W, H, SAMPLES = 32, 24, 4
 IDENTITY = (0.0, 0.0, 0.0, 1.0)
 HIT_DTYPE = np.dtype(nat.HIT_FIELDS)
+PER_PIXEL = dict(dof=0.0, lod_random=0.0, lod_samples=0.0)   # settings under which the ray table holds one record per pixel
+
+
+def instance(res_max, per_pixel, views=False):
+    """The first_hit_kernel instance a pass runs, with every template argument -- what the launch census must show for the call:
+    8 positions at resolution mode 0 / 1 for scenes of resolutions <= 1 / <= 2, 4 at the generic mode 2; the ray table's layout;
+    one camera or several."""
+    return "first_hit_kernel<%s,%d,%s>" % ({1: "8,0", 2: "8,1", 3: "4,2"}[res_max], bool(per_pixel), "true" if views else "false")
 
 
 def lens_of(st):
@@ -79,9 +87,11 @@ def assert_records_equal(got, exp):
     assert np.array_equal(got["pos"].view(np.uint64), exp["pos"].view(np.uint64))
 
 
-def check_against_oracle(sc, st, pos, rot, lens, grid=None, vacuous_ok=False):
+def check_against_oracle(sc, st, pos, rot, lens, runs=None, grid=None, vacuous_ok=False):
+    """runs: the instance the pass must launch, and no other (None: not asserted)."""
     cam = camera_for(id_scene(sc), settings_store(st), pos, rot, lens, grid=grid)
-    h = cam.first_hit(0, all_samples=True)
+    h, ran = launches_of(lambda: cam.first_hit(0, all_samples=True))
+    assert runs is None or ran == {runs}, (ran, runs)
     exp = oracle_hits(sc, st, pos, rot, lens, h.pixels, vacuous_ok)
     got = h.numpy()
     assert_records_equal(got, exp)
@@ -103,8 +113,8 @@ _case1 = {}
 def case1(per_pixel=False):
     if per_pixel not in _case1:
         sc, pos, rot, lens = raised_default()
-        st = ol.make_settings(width=W, height=H, samples=SAMPLES, **(dict(dof=0.0, lod_random=0.0, lod_samples=0.0) if per_pixel else {}))
-        cam, h, exp = check_against_oracle(sc, st, pos, rot, lens, grid=sc.grid_lod0)
+        st = ol.make_settings(width=W, height=H, samples=SAMPLES, **(PER_PIXEL if per_pixel else {}))
+        cam, h, exp = check_against_oracle(sc, st, pos, rot, lens, instance(2, per_pixel), grid=sc.grid_lod0)
         exp.setflags(write=False)
         _case1[per_pixel] = (cam, st, h, exp)
     return _case1[per_pixel]
@@ -127,8 +137,8 @@ def test_default_scene_against_the_oracle(per_pixel):
 def test_synth64_against_the_oracle(per_pixel):
     """A dense world at resolution 1 whose table is an identity table: the entries are computed, not read."""
     sc = ol.synth64_scene()
-    st = ol.make_settings(width=W, height=H, samples=SAMPLES, **(dict(dof=0.0, lod_random=0.0, lod_samples=0.0) if per_pixel else {}))
-    cam, h, exp = check_against_oracle(sc, st, sc.cam_pos, sc.cam_rot, sc.cam_lens)
+    st = ol.make_settings(width=W, height=H, samples=SAMPLES, **(PER_PIXEL if per_pixel else {}))
+    cam, h, exp = check_against_oracle(sc, st, sc.cam_pos, sc.cam_rot, sc.cam_lens, instance(1, per_pixel))
     c = cam._c_scene(cam._ensure_scene())
     assert int(c.max_resolution) == 1 and (int(c.flags) & nat.SCENE_TABLE_IS_IDENTITY)
     assert len(set(exp["material"][exp["material"] > 0].tolist())) == 13
@@ -151,11 +161,23 @@ def hand_scene():
     return ol.Scene(origin, dims, cs, present, res, ol.Scene.camera_grid(grid, origin, dims, cs, present, res), id_materials(5))
 
 
+HAND_POSE = ((2.3, 3.6, -14.45), IDENTITY)   # outside the box, looking at it
+
+
 @gpu
 def test_generic_resolutions_and_void_skipping():
     sc = hand_scene()
     st = ol.make_settings(width=W, height=H, samples=SAMPLES, chunk_size=8, dist_max=64)
-    cam, h, exp = check_against_oracle(sc, st, (2.3, 3.6, -14.45), IDENTITY, lens_of(st))   # outside the box, looking at it
+    cam, h, exp = check_against_oracle(sc, st, *HAND_POSE, lens_of(st), instance(3, False))
+    assert int(cam._c_scene(cam._ensure_scene()).max_resolution) == 3
+
+
+@gpu
+def test_generic_resolutions_with_one_ray_record_per_pixel():
+    """(the generic instance that reads one record per pixel: no other test runs it)"""
+    sc = hand_scene()
+    st = ol.make_settings(width=W, height=H, samples=SAMPLES, chunk_size=8, dist_max=64, **PER_PIXEL)
+    cam, h, exp = check_against_oracle(sc, st, *HAND_POSE, lens_of(st), instance(3, True))
     assert int(cam._c_scene(cam._ensure_scene()).max_resolution) == 3
 
 
@@ -178,7 +200,7 @@ def big_table_scene():
 def test_chunk_table_read_from_memory():
     sc = big_table_scene()
     st = ol.make_settings(width=16, height=12, samples=1, chunk_size=8, dist_max=64)
-    cam, h, exp = check_against_oracle(sc, st, (4.3, 0.6, -20.45), IDENTITY, lens_of(st))
+    cam, h, exp = check_against_oracle(sc, st, (4.3, 0.6, -20.45), IDENTITY, lens_of(st), instance(1, False))
     c = cam._c_scene(cam._ensure_scene())
     assert int(np.prod(sc.dims)) == 4352 > 4096 and not (int(c.flags) & nat.SCENE_TABLE_IS_IDENTITY)
 
@@ -192,8 +214,8 @@ def test_rotated_camera_and_dist_min():
     g = ol.load_render("rot")
     sc = ol.default_scene()
     st = ol.make_settings(width=W, height=H, samples=SAMPLES, dist_min=3)
-    check_against_oracle(sc, st, g["cam_pos"], g["cam_rot"], g["cam_lens"][0], grid=sc.grid_lod0, vacuous_ok=True)
-    check_against_oracle(sc, st, g["cam_pos"] + np.array([0.0, 10.0, 0.0]), g["cam_rot"], g["cam_lens"][0], grid=sc.grid_lod0)
+    check_against_oracle(sc, st, g["cam_pos"], g["cam_rot"], g["cam_lens"][0], instance(2, False), grid=sc.grid_lod0, vacuous_ok=True)
+    check_against_oracle(sc, st, g["cam_pos"] + np.array([0.0, 10.0, 0.0]), g["cam_rot"], g["cam_lens"][0], instance(2, False), grid=sc.grid_lod0)
 
 
 # ---- 5. consistency with the colour frame ----------------------------------------------------------------------------
@@ -289,9 +311,10 @@ def test_views_equal_single_passes(per_pixel, all_samples):
             set_pose(cam, p)
             single.append(cam.first_hit(0, all_samples=all_samples))
         set_pose(cam, poses[3])   # (the camera's own pose plays no part in a batch)
-        got = cam.first_hit_views(poses, all_samples=all_samples)
+        got, ran = launches_of(lambda: cam.first_hit_views(poses, all_samples=all_samples))
     finally:
         cam.pos, cam.rot = keep
+    assert ran == {instance(2, per_pixel, views=True)}, ran
     assert len(got) == 5
     for b, s in zip(got, single):
         assert_records_equal(b.numpy(), s.numpy())
@@ -300,6 +323,36 @@ def test_views_equal_single_passes(per_pixel, all_samples):
     assert got[0].stats is not None and int(got[0].stats[8]) == sum(int(s.stats[8]) for s in single)
     assert int(got[0].stats[4]) == sum(int(s.stats[4]) for s in single)
     assert (np.delete(got[0].stats, [4, 8]) == 0).all()
+
+
+@gpu
+@pytest.mark.parametrize("per_pixel", [False, True])
+@pytest.mark.parametrize("res_max", [1, 3])
+def test_views_of_the_other_resolution_modes_against_the_oracle(res_max, per_pixel):
+    """The batched instances no other test runs -- resolution mode 0 (synth64: resolution 1 throughout) and the generic mode
+    (the hand scene: resolutions 1, 2 and 3), with either layout of the ray table: three views each, every record of every view
+    against the oracle's, the first view's asserted not to be vacuous."""
+    if res_max == 1:
+        sc = ol.synth64_scene()
+        first, lens, kw = (tuple(sc.cam_pos), tuple(sc.cam_rot)), sc.cam_lens, {}
+    else:
+        sc = hand_scene()
+        first, kw = HAND_POSE, dict(chunk_size=8, dist_max=64)
+        lens = lens_of(ol.make_settings())
+    st = ol.make_settings(width=W, height=H, samples=SAMPLES, **kw, **(PER_PIXEL if per_pixel else {}))
+    rng = np.random.default_rng(50 + res_max)
+    poses = [first]
+    for _ in range(2):   # moved by a few cells and turned a little
+        q = np.array(first[1]) + rng.normal(size=4) * 0.1
+        poses.append((tuple(np.array(first[0]) + rng.uniform(-3, 3, 3)), tuple(q / np.linalg.norm(q))))
+    cam = camera_for(id_scene(sc), settings_store(st), *first, lens)
+    assert int(cam._c_scene(cam._ensure_scene()).max_resolution) == res_max
+    got, ran = launches_of(lambda: cam.first_hit_views(poses, all_samples=True))
+    assert ran == {instance(res_max, per_pixel, views=True)}, ran
+    assert len(got) == 3
+    for v, (pos, rot) in enumerate(poses):
+        assert_records_equal(got[v].numpy(), oracle_hits(sc, st, pos, rot, lens, got[v].pixels, vacuous_ok=v > 0))
+    assert len({tuple(g.numpy()["material"].tolist()) for g in got}) == 3   # three different views
 
 
 @gpu

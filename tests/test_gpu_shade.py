@@ -12,7 +12,7 @@ import pytest
 import cast_ref as cr
 import oracle_lib as ol
 import shade_ref as sr
-from gpu_util import camera_for, settings_store
+from gpu_util import camera_for, launches_of, settings_store
 from python_raytracer_amd import _native as nat
 from python_raytracer_amd import data
 
@@ -20,6 +20,11 @@ gpu = pytest.mark.gpu
 
 IDENTITY = (0.0, 0.0, 0.0, 1.0)
 _cams = {}
+# the instance a call runs, by the highest resolution of the scene's chunks and by whether it keeps records: what the launch
+# census must show for a shade_rays call
+SHADE_INSTANCE = {(1, True): 'shade_kernel<8,0,true>', (2, True): 'shade_kernel<8,1,true>', (3, True): 'shade_kernel<4,2,true>',
+                  (1, False): 'shade_kernel<8,0,false>', (2, False): 'shade_kernel<8,1,false>', (3, False): 'shade_kernel<4,2,false>'}
+RES_MAX = {"default_mb2": 2, "default_mb8": 2, "default_scaled_nobg": 2, "synth64_mb4": 1, "hand": 3, "big_table": 1}
 
 
 @contextlib.contextmanager
@@ -77,17 +82,18 @@ def test_against_the_oracle(name):
     sc, st, has_bg, origins, vels, lives, draws, exp, trav = sr.ray_set(name)
     cam = cam_of(name)
     with background(has_bg):
-        res = cam.shade_rays(origins, vels, lives, draws=draws)
+        res, ran = launches_of(lambda: cam.shade_rays(origins, vels, lives, draws=draws))
+        assert ran == {SHADE_INSTANCE[RES_MAX[name], True]}, (name, ran)   # the instance the set is there for, and no other
         check_result(res, exp)
         assert int(res.stats[11]) == 0
-        lean = cam.shade_rays(origins, vels, lives, draws=draws, want_records=False)
+        lean, ran = launches_of(lambda: cam.shade_rays(origins, vels, lives, draws=draws, want_records=False))
+        assert ran == {SHADE_INSTANCE[RES_MAX[name], False]}, (name, ran)
         assert lean.records is None and np.array_equal(rgba_of(lean), sr.packed(exp))
         assert np.array_equal(lean.stats[:11], sr.stats_of(exp))
         with pytest.raises(ValueError, match="records"):
             lean.exhausted_mask()
     c = cam._c_scene(cam._ensure_scene())
-    if name != "big_table":
-        assert int(c.max_resolution) == {"hand": 3, "synth64_mb4": 1}.get(name, 2)
+    assert int(c.max_resolution) == RES_MAX[name]
     if name == "big_table":
         assert int(np.prod(sc.dims)) == 4352 > 4096 and not (int(c.flags) & nat.SCENE_TABLE_IS_IDENTITY)
     if name == "synth64_mb4":

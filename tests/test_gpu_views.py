@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
-from gpu_util import HANDOUT_KNOBS, camera_for, run_children, settings_store, sparse_scene
+from gpu_util import HANDOUT_KNOBS, camera_for, launches_of, run_children, settings_store, sparse_scene
 from python_raytracer_amd import _native as nat
 
 gpu = pytest.mark.gpu
@@ -29,6 +29,12 @@ POSES = [
     ((5000.5, 4000.5, -3000.5), IDENTITY),     # far outside the world: every ray ends in the sky
     ((0.3, 0.6, -10.45), IDENTITY),            # the first again
 ]
+
+
+# The instance a batch's march runs, by the highest resolution of the scene's chunks, and the two re-trace instances every batch
+# launches behind it (they return at once when their lists are empty): what the launch census must show for a render_views call
+VIEWS_INSTANCE = {1: 'march_views_kernel<8,0,false,0>', 2: 'march_views_kernel<8,1,false,0>', 3: 'march_views_kernel<4,2,false,0>'}
+VIEWS_RETRACES = {'march_views_kernel<4,2,true,1>', 'march_views_kernel<4,2,true,2>'}
 
 
 def settings(**kw):
@@ -104,7 +110,8 @@ def test_batch_equals_single_frames(res_max):
     assert (W * H * smax) % 64 != 0
     assert (ref[0].ray_rgba.cpu().numpy().reshape(-1, smax)[:, -1] == 0).any(), "no pixel with fewer than smax samples"
     set_pose(cam, POSES[2])   # (the camera's own pose plays no part in a batch)
-    got = cam.render_views(POSES, want_ray_rgba=True)
+    got, ran = launches_of(lambda: cam.render_views(POSES, want_ray_rgba=True))
+    assert ran == {VIEWS_INSTANCE[res_max]} | VIEWS_RETRACES, ran   # the instance the parametrisation names, and no other
     assert len(got) == len(POSES)
     for b, s in zip(got, ref):
         assert_view_equals_single(b, s, CS)
@@ -123,12 +130,13 @@ def test_batch_equals_single_frames(res_max):
 
 
 @gpu
-@pytest.mark.parametrize("res_max", [2, 3])
+@pytest.mark.parametrize("res_max", [1, 2, 3])
 def test_batch_against_the_oracle(res_max):
     st = settings()
     sc = scene(res_max)
     cam = camera_for(sc, settings_store(st), *POSES[0], lens_of(st))
-    got = cam.render_views(POSES, want_ray_rgba=True)
+    got, ran = launches_of(lambda: cam.render_views(POSES, want_ray_rgba=True))
+    assert ran == {VIEWS_INSTANCE[res_max]} | VIEWS_RETRACES, ran
     px = got[0].pixels
     for v in (1, 2):   # the rotated camera, the one beside the chunk faces
         o = ol.render(sc, st, POSES[v][0], POSES[v][1], lens_of(st), px, libm=ol.LIBM_PORTABLE)
@@ -324,7 +332,8 @@ def test_retraces_in_a_batch():
     assert all(int(s.stats[9]) > 0 for s in ref), [int(s.stats[9]) for s in ref]
     assert max(int(s.stats[5]) for s in ref) > 0
     cam.fast_draws = 32
-    got = cam.render_views(poses, want_ray_rgba=True)
+    got, ran = launches_of(lambda: cam.render_views(poses, want_ray_rgba=True))
+    assert ran == {VIEWS_INSTANCE[1]} | VIEWS_RETRACES, ran   # (the two re-trace instances with work to do: stats[9], and below)
     assert int(got[0].stats[9]) > 0
     for b, s in zip(got, ref):
         assert_view_equals_single(b, s, CS)

@@ -170,3 +170,69 @@ def test_march_variant_diagnostic_is_exported_and_checks_its_arguments():
     assert name.value == b"march_kernel<4,0,false,false,0,0,false,false,0>" and list(eff) == [0, 0, 0]
     for key, bad in (("resmode", 3), ("resmode", -1), ("per_pixel", 3), ("lookup", 3), ("lookup", -1), ("trav_words", -1)):
         assert nat.march_variant(**{key: bad})[0] == ERR_ARG, (key, bad)
+
+
+# ---- the launch census (vrt_diag_launch_census, _native.launch_census) ------------------------------------------------------
+# The instances of the families a launch chooses by resolution mode alone (VRT_BY_RES in csrc/vrt_kernels.hip) and the two
+# re-trace instances of the batched views, with every template argument: the census' rows behind the march table's.
+BY_RES_NAMES = [
+    'march_views_kernel<8,0,false,0>', 'march_views_kernel<8,1,false,0>', 'march_views_kernel<4,2,false,0>',
+    'march_views_kernel<4,2,true,1>', 'march_views_kernel<4,2,true,2>',
+    'first_hit_kernel<8,0,1,false>', 'first_hit_kernel<8,0,0,false>', 'first_hit_kernel<8,1,1,false>', 'first_hit_kernel<8,1,0,false>',
+    'first_hit_kernel<4,2,1,false>', 'first_hit_kernel<4,2,0,false>',
+    'first_hit_kernel<8,0,1,true>', 'first_hit_kernel<8,0,0,true>', 'first_hit_kernel<8,1,1,true>', 'first_hit_kernel<8,1,0,true>',
+    'first_hit_kernel<4,2,1,true>', 'first_hit_kernel<4,2,0,true>',
+    'cast_kernel<8,0>', 'cast_kernel<8,1>', 'cast_kernel<4,2>',
+    'shade_kernel<8,0,true>', 'shade_kernel<8,1,true>', 'shade_kernel<4,2,true>',
+    'shade_kernel<8,0,false>', 'shade_kernel<8,1,false>', 'shade_kernel<4,2,false>',
+]
+UNSELECTED = 'march_kernel<4,2,false,false,0,4,false,false,0>'   # the table's one row no launch selects
+
+
+def census_row(L, row, cap=128):
+    name, count = C.create_string_buffer(b"?" * (cap - 1), cap), C.c_int64(-7)
+    return L.vrt_diag_launch_census(row, name, cap, C.byref(count)), name.value.decode(), count.value
+
+
+def test_launch_census_is_exported_and_checks_its_arguments():
+    """Outside include/vrt.h and _native.EXPORTS (no ABI change); callable without a GPU; a refusal writes nothing."""
+    L = nat.lib()
+    assert "vrt_diag_launch_census" not in nat.EXPORTS and L.vrt_abi_version() == 9
+    assert "vrt_diag_launch_census" not in open(kr.SRC.replace("python_raytracer_amd/csrc/vrt_kernels.hip", "include/vrt.h")).read()
+    n, first, count = census_row(L, 0)
+    assert n == 74 + len(BY_RES_NAMES) and first == 'march_kernel<4,2,true,false,0,4,false,false,0>' and count >= 0
+    name, cnt = C.create_string_buffer(b"?" * 127, 128), C.c_int64(-7)
+    for row, nm, cap, ct in ((-1, name, 128, cnt), (n, name, 128, cnt), (1 << 30, name, 128, cnt), (0, None, 128, cnt),
+                             (0, name, 128, None), (0, name, 0, cnt), (0, name, -5, cnt), (0, name, len(first), cnt)):
+        assert L.vrt_diag_launch_census(row, nm, cap, C.byref(ct) if ct is not None else None) == ERR_ARG, (row, cap)
+        assert name.value == b"?" * 127 and cnt.value == -7, (row, cap)
+    assert L.vrt_diag_launch_census(0, name, len(first) + 1, C.byref(cnt)) == n and name.value.decode() == first
+
+
+def test_launch_census_rows_are_the_table_and_the_by_resolution_instances():
+    """Row for row: the march table in its order -- its names are the ones vrt_diag_march_variant gives for ROWS, plus the one
+    row no launch selects -- then the by-resolution families."""
+    L = nat.lib()
+    n = census_row(L, 0)[0]
+    names = [census_row(L, row)[1] for row in range(n)]
+    src = open(kr.SRC).read()
+    table = re.findall(r"^    X\((\d), (\w+), (\d), (\w+), (\w+), (\d), (\d), (\w+), (\w+), (\w+), (\d)\)", src, re.M)
+    assert len(names) == len(set(names)) == len(table) + len(BY_RES_NAMES)
+    march, by_res = names[:len(table)], names[len(table):]
+    chosen = {nat.march_variant(**inputs)[1] for _, inputs, name, _ in ROWS if name}
+    assert set(march) == chosen | {UNSELECTED} and UNSELECTED not in chosen
+    assert by_res == BY_RES_NAMES
+    assert list(nat.launch_census()) == names
+
+
+def test_launch_census_counts_nothing_in_a_process_that_launched_nothing():
+    """(in a child: this process may have rendered before)  Asking the chooser is no launch."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, "-c", "from python_raytracer_amd import _native as nat\nnat.march_variant(pool=1)\n"
+                          "c = nat.launch_census()\nprint('CENSUS', len(c), sum(c.values()), min(c.values()))"],
+                         cwd=root, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert [l for l in out.stdout.splitlines() if l.startswith("CENSUS")] == ["CENSUS %d 0 0" % (74 + len(BY_RES_NAMES))]
