@@ -149,6 +149,8 @@ enum { VRT_S_RAYS = 8, VRT_S_RNG_RETRACED = 9, VRT_S_RNG_EXHAUSTED = 10, VRT_S_T
                                      themselves (vrt_render_tile without d_ray_table: no ray table is written then) */
        VRT_S_CAST_REJECTED = 9,  /* vrt_cast_rays only (which re-traces nothing: the index is free there): rays the device
                                     refused -- see vrt_cast_ray */
+       VRT_S_PATH_TRUNCATED = 12,  /* vrt_path_rays only (which has no ray pool): completed rays with more hits than max_hits */
+       VRT_S_PATH_RECORDS = 13,    /* vrt_path_rays only: hit records written for completed rays */
        VRT_NSTATS = 16 };
 
 int vrt_abi_version(void);
@@ -414,6 +416,56 @@ int vrt_shade_workspace_bytes(int64_t n_rays, int64_t* bytes);
 int vrt_shade_rays(const vrt_scene* scene, const vrt_settings* st, const vrt_cast_ray* d_rays, int64_t n_rays,
                    double max_life, const double* d_draws, int32_t n_draws, void* d_workspace, int64_t workspace_bytes,
                    uint32_t* d_rgba, vrt_ray* d_records, uint64_t* d_stats, const vrt_traversed* trav, void* stream);
+
+/* ---- hit paths of explicit rays -----------------------------------------------------------------------------
+ * Every voxel a ray SHADES, not only the first: picking through glass, the object a mirror shows, multi-return range
+ * sensors, audio paths with their reflections, "which voxels lit this probe".  vrt_shade_rays's rays, start state, loop,
+ * draws, validation and max_life; in front of every lib.material (init.py:78-79) the ray's state is stored as one vrt_hit
+ * -- step, pos, cell = floor(pos), the material found -- which is exactly what vrt_cast_rays stores for the first one.
+ *   d_hits    [n_rays][max_hits] vrt_hit: record j of ray i is its j-th hit (from 0) for j < min(count, max_hits); the
+ *             other slots of the row hold the unused record (material -1, every other field 0, as vrt_first_hit marks an
+ *             unused sample slot).  The records of a row are in the order the ray met them: step never decreases.
+ *   d_counts  [n_rays] int32: all hits of the ray (its counters[VRT_C_HIT] in vrt_shade_rays), which may exceed max_hits
+ *             -- the row then holds the first max_hits; -2 a rejected ray, -3 a ray whose draws ran out.
+ *   d_rgba    [n_rays] uint32 as in vrt_shade_rays, or NULL.
+ *   max_hits  1..64, and n_rays * max_hits < 2^31.
+ *   Rejection.  vrt_cast_rays's rule (see vrt_cast_ray), per ray on the device: d_counts[i] = -2, every slot of the row unused,
+ *             d_rgba[i] = 0, counted in d_stats[VRT_S_CAST_REJECTED]; the ray is never marched.
+ *   Exhaustion.  A ray that needs more draws than n_draws is not completed and reports nothing: d_counts[i] = -3, every slot
+ *             of the row unused (what the ray had stored is overwritten), d_rgba[i] = 0, counted in
+ *             d_stats[VRT_S_RNG_EXHAUSTED] and not in d_stats[VRT_S_RAYS].
+ *   d_stats   [VRT_NSTATS] uint64, zeroed by the callee: [0..10] as in vrt_shade_rays, [11] 0 (there is no traversed box),
+ *             [12] (VRT_S_PATH_TRUNCATED) completed rays with more hits than max_hits, [13] (VRT_S_PATH_RECORDS) hit records
+ *             written for completed rays = sum of min(count, max_hits), [14..15] 0.
+ *   d_workspace: vrt_path_workspace_bytes() bytes, as for vrt_shade_rays; nothing per ray.
+ * Every byte of d_hits, d_counts and d_rgba is defined when the call has run.  d_rgba and d_stats[0..10] are bit for bit
+ * what vrt_shade_rays gives for the same rays and draws; run that call on the same rays for vrt_ray records or a traversed
+ * box, which this one does not write.  d_hits rows are what vrt_hit_owners takes.
+ * n_rays = 0 only zeroes the statistics; n_rays >= 2^32 - 1, max_hits outside 1..64, n_rays * max_hits >= 2^31, a NULL or
+ * misaligned d_hits (8 bytes) or d_counts (4 bytes) with n_rays > 0 are VRT_ERR_ARG; more than 2^28 rays are split into
+ * launches.  Every argument is checked before any HIP call; nothing is allocated or synchronised, so a call may be captured
+ * into a hipGraph.  Not offered: the mix weight of each hit, the ray pool, paths inside vrt_render_tile. */
+int vrt_path_workspace_bytes(int64_t n_rays, int64_t* bytes);
+int vrt_path_rays(const vrt_scene* scene, const vrt_settings* st, const vrt_cast_ray* d_rays, int64_t n_rays,
+                  double max_life, const double* d_draws, int32_t n_draws, int32_t max_hits, void* d_workspace,
+                  int64_t workspace_bytes, vrt_hit* d_hits, int32_t* d_counts, uint32_t* d_rgba, uint64_t* d_stats,
+                  void* stream);
+
+/* The primary rays of a frame as vrt_cast_ray records: what turns "pixel (x, y), sample s of this camera" into a ray that
+ * vrt_cast_rays, vrt_shade_rays and vrt_path_rays take.  The arguments are vrt_first_hit's; d_rays[k] (64-byte aligned,
+ * n_px * max_samples records, or n_px with first_sample_only) is the start state vrt_first_hit and vrt_render_tile give ray
+ * slot k -- vel from the ray table's lens quaternion and cam->rot, origin = cam->pos + vel * dist_min, life from the ray
+ * table, reserved 0 -- computed by the same device code, so the doubles are bit for bit the frame's.  An unused sample slot
+ * gets eight NaNs, which every explicit-ray call rejects.  No voxel is read.
+ *   d_stats   [VRT_NSTATS] uint64, zeroed by the callee: word 8 (VRT_S_RAYS) = records that hold a ray, every other word 0.
+ * The colour frame's ray (x, y, s) consumed first_draw draws of its row before its loop began (1: lod_random; 3 with
+ * dof != 0: the lens jitter too), so vrt_shade_rays or vrt_path_rays with d_draws row k = that row from column first_draw
+ * on reproduces the frame's per-ray colour.
+ * The range rule is vrt_render_tile's and is checked before any HIP call; nothing is allocated or synchronised, so a call
+ * may be captured into a hipGraph. */
+int vrt_pixel_rays(const vrt_scene* scene, const vrt_settings* st, const vrt_camera* cam, const int32_t* d_pixels_xy,
+                   int64_t n_px, const void* d_plan, int64_t n_distinct, const double* d_ray_table,
+                   int32_t first_sample_only, vrt_cast_ray* d_rays, uint64_t* d_stats, void* stream);
 
 /* Camera.trace (init.py:37-121) for explicit rays: direction (dir_x, dir_y), detail and the random draws the
  * ray may consume (d_draws[i * n_draws + k] = k-th random.random() of ray i).  d_rays[i].counters[VRT_C_DRAW]

@@ -112,7 +112,10 @@ class VrtCastRay(C.Structure):
 CAST_RAY_BYTES = 64
 HIT_REJECTED = -2   # vrt_hit.material of a ray vrt_cast_rays refused
 RAY_REJECTED, RAY_EXHAUSTED = -2, -3   # vrt_ray.s of a ray vrt_shade_rays refused / whose draws ran out
-
+PATH_REJECTED, PATH_EXHAUSTED = -2, -3   # d_counts of a ray vrt_path_rays refused / whose draws ran out
+HIT_UNUSED = -1   # vrt_hit.material of an unused sample slot (vrt_first_hit) or an unused slot of a ray's row (vrt_path_rays)
+PATH_MAX_HITS = 64   # vrt_path_rays: hit records kept per ray at most
+S_PATH_TRUNCATED, S_PATH_RECORDS = 12, 13   # vrt_path_rays only: completed rays with more hits than max_hits / records written
 
 
 class VrtOwner(C.Structure):
@@ -195,6 +198,14 @@ def lib():
     L.vrt_shade_rays.restype = C.c_int
     L.vrt_shade_rays.argtypes = [C.POINTER(VrtScene), C.POINTER(VrtSettings), vp, i64, C.c_double, vp, i32, vp, i64, vp, vp, vp,
                                  C.POINTER(VrtTraversed), vp]
+    L.vrt_path_workspace_bytes.restype = C.c_int
+    L.vrt_path_workspace_bytes.argtypes = [i64, C.POINTER(i64)]
+    L.vrt_path_rays.restype = C.c_int
+    L.vrt_path_rays.argtypes = [C.POINTER(VrtScene), C.POINTER(VrtSettings), vp, i64, C.c_double, vp, i32, i32, vp, i64, vp, vp, vp,
+                                vp, vp]
+    L.vrt_pixel_rays.restype = C.c_int
+    L.vrt_pixel_rays.argtypes = [C.POINTER(VrtScene), C.POINTER(VrtSettings), C.POINTER(VrtCamera), vp, i64, vp, i64, vp, i32,
+                                 vp, vp, vp]
     L.vrt_draw_table_bytes.restype = C.c_int
     L.vrt_draw_table_bytes.argtypes = [i64, i32, C.POINTER(i64)]
     L.vrt_draw_table_build.restype = C.c_int
@@ -258,7 +269,7 @@ EXPORTS = ["vrt_abi_version", "vrt_status_string", "vrt_last_hip_error", "vrt_de
            "vrt_max_samples", "vrt_plan_bytes", "vrt_plan_build", "vrt_workspace_bytes", "vrt_render_tile",
            "vrt_views_workspace_bytes", "vrt_render_views",
            "vrt_first_hit", "vrt_first_hit_views_workspace_bytes", "vrt_first_hit_views", "vrt_cast_rays",
-           "vrt_shade_workspace_bytes", "vrt_shade_rays",
+           "vrt_shade_workspace_bytes", "vrt_shade_rays", "vrt_path_workspace_bytes", "vrt_path_rays", "vrt_pixel_rays",
            "vrt_draw_table_bytes", "vrt_draw_table_build", "vrt_ray_table_bytes", "vrt_ray_table_build",
            "vrt_pow_memo_create", "vrt_occupancy_build", "vrt_canvas_blit", "vrt_world_tables_bytes", "vrt_world_tables_build",
            "vrt_trace_workspace_bytes", "vrt_trace_rays", "vrt_rng_draws",

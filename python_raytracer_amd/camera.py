@@ -14,7 +14,7 @@ from . import _native as nat
 from . import data as _data
 from .lib import vec3, quaternion, rgb, store, is_default_background
 from .scene import PackedScene
-from .results import RenderResult, HitResult, CastResult, ShadeResult, _traversed_positions
+from .results import RenderResult, HitResult, CastResult, ShadeResult, PathResult, _traversed_positions
 
 
 def _xyz(v):
@@ -950,6 +950,49 @@ class Camera:
             raise ValueError("shade_rays: the traversed box %r has more than 2**28 cells" % (dims,))
         return self._key_box(origin, dims)
 
+    def _shaded_setup(self, who, max_life, seeds, draws, n_draws):
+        """What shade_rays and path_rays (`who`) check and prepare before they enter their stream: (max_life, n_draws, the
+        scene, C settings).  The pow memo of the camera's falloff is made here, outside any stream capture."""
+        torch = self._torch
+        dev = self._require_device()
+        s = self._settings()
+        max_life = _max_life(max_life, s.dist_max, who)
+        if seeds is not None and draws is not None:
+            raise ValueError(who + ": pass seeds or draws, not both")
+        if seeds is not None:
+            n_draws = 32 if n_draws is None else int(n_draws)
+            if not 2 <= n_draws <= 4096:
+                raise ValueError(who + ": n_draws must lie in 2..4096, not %r" % n_draws)
+        sc = self._ensure_scene()
+        st = self._c_settings(0)
+        if not torch.cuda.is_current_stream_capturing():
+            _ensure_pow_memo(torch, dev, s.falloff)
+        return max_life, n_draws, sc, st
+
+    def _shaded_inputs(self, who, origins, velocities, lives, seeds, draws, n_draws):
+        """The device inputs of shade_rays and path_rays (`who`), made on the current stream: (vrt_cast_ray records [n, 8], n,
+        draws [n, n_draws] or None, n_draws, the stream's handle).  seeds: the rows are made on the device (vrt_rng_draws)."""
+        torch = self._torch
+        dev = self._device
+        s = self._settings()
+        rec = self._cast_records(origins, velocities, lives, float(s.dist_max) - float(s.dist_min), who)
+        n = int(rec.shape[0])
+        if n == 0:
+            raise ValueError(who + ": no rays")
+        if n >= (1 << 32) - 1:
+            raise ValueError(who + ": 2**32 - 1 rays and more need several calls")
+        cur = torch.cuda.current_stream().cuda_stream
+        if seeds is not None:
+            sd = _seeds(seeds, n, who, dev)
+            dd = torch.empty((n, n_draws), dtype=torch.float64, device=dev)
+            nat.check(nat.lib().vrt_rng_draws(sd.data_ptr(), n, n_draws, dd.data_ptr(), cur), "vrt_rng_draws")
+        elif draws is not None:
+            dd = _floats(draws, "draws", who, (n, "n_draws" if n_draws is None else int(n_draws)), dev).contiguous()
+            n_draws = int(dd.shape[1])
+        else:
+            dd, n_draws = None, 0
+        return rec, n, dd, n_draws, cur
+
     def shade_rays(self, origins, velocities=None, lives=None, *, seeds=None, draws=None, n_draws=None, max_life=None,
                    want_records=True, want_traversed=False, stream=None):
         """Colour and end state along explicit rays (vrt_shade_rays): ray k starts at origins[k] with velocity velocities[k]
@@ -974,35 +1017,9 @@ class Camera:
         torch = self._torch
         L = nat.lib()
         dev = self._require_device()
-        s = self._settings()
-        max_life = _max_life(max_life, s.dist_max, "shade_rays")
-        if seeds is not None and draws is not None:
-            raise ValueError("shade_rays: pass seeds or draws, not both")
-        if seeds is not None:
-            n_draws = 32 if n_draws is None else int(n_draws)
-            if not 2 <= n_draws <= 4096:
-                raise ValueError("shade_rays: n_draws must lie in 2..4096, not %r" % n_draws)
-        sc = self._ensure_scene()
-        st = self._c_settings(0)
-        if not torch.cuda.is_current_stream_capturing():
-            _ensure_pow_memo(torch, dev, s.falloff)
+        max_life, n_draws, sc, st = self._shaded_setup("shade_rays", max_life, seeds, draws, n_draws)
         with torch.cuda.device(dev), self._on_stream(stream):
-            rec = self._cast_records(origins, velocities, lives, float(s.dist_max) - float(s.dist_min), "shade_rays")
-            n = int(rec.shape[0])
-            if n == 0:
-                raise ValueError("shade_rays: no rays")
-            if n >= (1 << 32) - 1:
-                raise ValueError("shade_rays: 2**32 - 1 rays and more need several calls")
-            cur = torch.cuda.current_stream().cuda_stream
-            if seeds is not None:
-                sd = _seeds(seeds, n, "shade_rays", dev)
-                dd = torch.empty((n, n_draws), dtype=torch.float64, device=dev)
-                nat.check(L.vrt_rng_draws(sd.data_ptr(), n, n_draws, dd.data_ptr(), cur), "vrt_rng_draws")
-            elif draws is not None:
-                dd = _floats(draws, "draws", "shade_rays", (n, "n_draws" if n_draws is None else int(n_draws)), dev).contiguous()
-                n_draws = int(dd.shape[1])
-            else:
-                dd, n_draws = None, 0
+            rec, n, dd, n_draws, cur = self._shaded_inputs("shade_rays", origins, velocities, lives, seeds, draws, n_draws)
             csc = self._c_scene(sc)
             tr, keys = self._shade_box(want_traversed)
             rgba = torch.empty(n, dtype=torch.uint32, device=dev)
@@ -1022,6 +1039,71 @@ class Camera:
         res = ShadeResult(rgba, records, stats, trav)
         res._workspace = ws
         return res
+
+    # ------------------------------------------------------------------ explicit rays: every voxel a ray shades
+    def path_rays(self, origins, velocities=None, lives=None, *, seeds=None, draws=None, n_draws=None, max_hits=8, max_life=None,
+                  want_rgba=True, stream=None):
+        """Every voxel explicit rays shade, not only the first (vrt_path_rays): shade_rays's rays, loop, draws and rejection
+        rule, with the ray's state -- step, pos, cell, material -- recorded in front of every lib.material: what stands behind
+        a pane of glass, what a mirror shows, the returns of a range sensor, the voxels that lit a probe.
+        origins, velocities, lives, seeds, draws, n_draws, max_life: as shade_rays takes them.
+        max_hits: records kept per ray, 1..64 (and n * max_hits < 2**31); `counts` holds all hits of a ray and may exceed it.
+        A rejected ray has count -2, one whose draws ran out count -3; both have every slot unused and rgba 0.
+        Returns a PathResult of device tensors, whose `records` DeviceWorld.owners takes as they are; rgba and stats[0..10]
+        are bit for bit shade_rays's.  Nothing is copied to the host and nothing synchronises (with tensors already on the
+        device the call can be captured into a graph)."""
+        torch = self._torch
+        L = nat.lib()
+        dev = self._require_device()
+        max_hits = int(max_hits)
+        if not 1 <= max_hits <= nat.PATH_MAX_HITS:
+            raise ValueError("path_rays: max_hits must lie in 1..%d, not %r" % (nat.PATH_MAX_HITS, max_hits))
+        max_life, n_draws, sc, st = self._shaded_setup("path_rays", max_life, seeds, draws, n_draws)
+        with torch.cuda.device(dev), self._on_stream(stream):
+            rec, n, dd, n_draws, cur = self._shaded_inputs("path_rays", origins, velocities, lives, seeds, draws, n_draws)
+            if n * max_hits >= 1 << 31:
+                raise ValueError("path_rays: %d rays of %d records each: n * max_hits must stay below 2**31" % (n, max_hits))
+            csc = self._c_scene(sc)
+            records = torch.empty(n * max_hits * nat.HIT_BYTES, dtype=torch.uint8, device=dev)
+            counts = torch.empty(n, dtype=torch.int32, device=dev)
+            rgba = torch.empty(n, dtype=torch.uint32, device=dev) if want_rgba else None
+            stats = torch.empty(nat.NSTATS, dtype=torch.int64, device=dev)   # (the library clears it)
+            nb = C.c_int64(0)
+            nat.check(L.vrt_path_workspace_bytes(n, C.byref(nb)), "vrt_path_workspace_bytes")
+            ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)   # (the call's own, kept by the result: shade_rays)
+            rc = L.vrt_path_rays(C.byref(csc), C.byref(st), rec.data_ptr(), n, max_life, dd.data_ptr() if n_draws else None,
+                                 n_draws, max_hits, ws.data_ptr(), ws.numel(), records.data_ptr(), counts.data_ptr(),
+                                 rgba.data_ptr() if want_rgba else None, stats.data_ptr(), cur)
+            nat.check(rc, "vrt_path_rays")
+        res = PathResult(records, counts, rgba, stats, max_hits)
+        res._workspace = ws
+        return res
+
+    def pixel_rays(self, thread=0, pixels=None, all_samples=False, stream=None):
+        """The primary rays of render() as explicit rays (vrt_pixel_rays): (rays, used) -- rays a [n, 8] float64 CUDA tensor of
+        vrt_cast_ray records that cast_rays, shade_rays and path_rays take as they are, one per pixel of settings.pixels[thread]
+        (or of an explicit pixel list; its first sample), or with all_samples one per ray slot p * max_samples + s; used a
+        bool [n] tensor, false for an unused sample slot, whose record is eight NaNs (rejected by every explicit-ray call).
+        Record k is the start state first_hit() and render() give that ray -- the same lens jitter, the same life, bit for
+        bit.  Nothing is copied to the host and nothing synchronises; `stream` defaults to the current one."""
+        torch = self._torch
+        L = nat.lib()
+        dev = self._require_device()
+        self._ensure_scene()   # (on the caller's stream: first_hit)
+        with torch.cuda.device(dev), self._on_stream(stream):
+            dp, st, csc, smax, n_px = self._frame_setup(thread, pixels)
+            cam = self._c_camera()
+            samples = smax if all_samples else 1
+            rtab, retire = self._first_hit_tables(dp, st)
+            rays = torch.empty((max(n_px * samples, 1), 8), dtype=torch.float64, device=dev)[: n_px * samples]
+            stats = torch.empty(nat.NSTATS, dtype=torch.int64, device=dev)   # (the library clears it)
+            rc = L.vrt_pixel_rays(C.byref(csc), C.byref(st), C.byref(cam), dp.tensor.data_ptr(), n_px, dp.plan.data_ptr(),
+                                  dp.n_distinct, rtab.data_ptr(), 0 if all_samples else 1, rays.data_ptr(), stats.data_ptr(),
+                                  torch.cuda.current_stream().cuda_stream)
+            retire()
+            nat.check(rc, "vrt_pixel_rays")
+            used = rays[:, 6] == rays[:, 6]   # (an unused slot is NaN throughout)
+        return rays, used
 
     def line_of_sight(self, a, b, stream=None):
         """torch.bool [n]: can point a[k] see point b[k]?  One cast per pair: vel = (b - a) / max|b - a| -- the reference's

@@ -806,7 +806,9 @@ struct MarchParams {
         int32_t prefix_draws;    // LIST: > 0 = the frame's march counted a re-traced ray's events up to the hit at which
                                  // a row of this many draws ran out; the re-trace takes them off again (hit_body)
         int32_t slot_stride;     // first_hit_kernel only: record k of the launch is ray slot ray0 + k * slot_stride (1, or the
-    };                           // sample slots per pixel when only every pixel's first sample is marched)
+                                 // sample slots per pixel when only every pixel's first sample is marched)
+        int32_t max_hits;        // path_kernel only: hit records kept per ray
+    };
     int32_t ct_cells;            // > 0: the chunk table (that many cells) is copied to LDS
     int32_t ct_identity;         // the chunk table is (i + 1) | 1 << 24 (VRT_SCENE_TABLE_IS_IDENTITY): computed, not read
     int32_t trav_words;          // > 0: per-wave settled bitmaps of that many 32-bit words in LDS
@@ -824,11 +826,16 @@ struct MarchParams {
     uint32_t* ray_rgba;          // [rays of the tile] packed result (tile mode)
     union {
         vrt_ray* rays;           // debug records (may be NULL)
-        vrt_hit* hits;           // first_hit_kernel only (which keeps no debug records): the launch's first-hit records
+        vrt_hit* hits;           // first_hit_kernel only (which keeps no debug records): the launch's first-hit records;
+                                 // path_kernel: [rays][max_hits] records of the whole call (indexed from ray 0, like ray_rgba)
+        vrt_cast_ray* out_rays;  // pixel_rays_kernel only: the launch's ray records
     };
     uint64_t* stats;
     uint32_t* retrace_list;      // rays whose draws ran out are appended here (may be NULL)
-    uint32_t* retrace_count;
+    union {
+        uint32_t* retrace_count;
+        int32_t* path_counts;    // path_kernel only (which has no re-trace list: retrace_list is NULL): hits per ray
+    };
     unsigned long long* pow_global;  // [2 * VRT_PW_SLOTS]: keys then values, shared by every workgroup
     unsigned long long* queue_head;  // launch-wide ray counter (zeroed before every launch)
     // tiled hand-out (march_pool_kernel, scenes beyond the caches; see tile_ticket): the whole window's rays are handed out as
@@ -6264,6 +6271,301 @@ int vrt_synth_volume(int32_t n, int32_t cs, uint32_t* d_chunk_table, uint8_t* d_
     int64_t nc = (int64_t)(n / cs) * (n / cs) * (n / cs);
     hipLaunchKernelGGL(synth_table_kernel, dim3(grid_for(nc)), dim3(VRT_BLOCK), 0, stream, nc, d_chunk_table);
     hipLaunchKernelGGL(synth_kernel, dim3(8192), dim3(VRT_BLOCK), 0, stream, (int)n, (int)cs, d_voxels);
+    HIP_TRY(hipGetLastError());
+    return VRT_OK;
+}
+
+}  // extern "C"
+
+// ---- path_kernel: every voxel an explicit ray shades (vrt_path_rays) -------------------------------------------------------
+// (This section stands behind every other kernel and launch site of the file, and its instances are not in the census: the
+// compiler emits kernels in the order it first meets them, an instance's code is not quite independent of its place in
+// that order, and the figures of the kernels above are pinned.)
+// shade_kernel's schedule and bodies without the vrt_ray records and without a traversed box: the hand-out, cast_ray_ok, the
+// start state, march_step, hit_body, ended_body, the t_hit / t_end thresholds and the prologue are that kernel's.  What a
+// lane in LANE_HIT holds when it is served IS the record write_hit stores for cast_kernel -- r.step, r.pos, floor(pos),
+// the material in the colour word's top byte -- and cnt[C_HIT] is the hit's index, so the record goes to
+// hits[ray * max_hits + cnt[C_HIT]] in front of hit_body while there is room.  A ray that ends has its count written and
+// the slots it did not use marked (material -1, every other field 0); a rejected ray (count -2) and one whose draws ran out
+// (count -3: what it had stored is overwritten) have all of them marked and rgba 0.  MarchParams carries max_hits where a
+// re-trace carries its prefix, the records where a frame carries its debug records and the counts where it carries the
+// re-trace count (retrace_list is NULL, so ended_body never reads that word).
+// (not inlined, like shade_mark: the stores in front of both the refill and the ENDED body cost vector registers)
+__device__ __noinline__ void path_close(const __attribute__((address_space(4))) MarchParams& Q, uint32_t ray, int count) {
+    Q.path_counts[ray] = count;
+    if (count < 0 && Q.ray_rgba) Q.ray_rgba[ray] = 0;
+    const int max_hits = Q.max_hits;
+    vrt_hit* h = Q.hits + (int64_t)ray * max_hits;
+    // (8-byte stores, write_hit's: 16-byte stores into an array aligned for them were measured and changed nothing -- DESIGN.md 4g)
+    for (int j = count < 0 ? 0 : count; j < max_hits; j++) write_hit(h + j, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, -1);
+}
+template <int SPEC, int RESMODE>
+__global__ void __launch_bounds__(VRT_BLOCK, VRT_WAVES_PER_SIMD) path_kernel(MarchParams P) {
+    static_assert(SPEC >= 4 && SPEC <= 16, "speculation depth");
+    __shared__ MarchShared S;
+    extern __shared__ __align__(16) unsigned char s_dyn[];
+    MarchCtx C;
+    march_prologue<false, RESMODE == 2>(P, S, s_dyn, C);  // (TD_ARGS: see shade_kernel)
+    C.vw = nullptr;
+    __syncthreads();
+
+    const int wave_in_block = threadIdx.x >> 6;
+    // (the hand-out is HandOut's, written out as in shade_kernel)
+    const int64_t count = P.n;
+    const int64_t chunk = P.chunk;
+    int64_t next = 0, range_end = 0;
+    bool more = true;  // the launch-wide counter may still have rays
+    if (chunk == 0) {  // static contiguous range per wave
+        const int64_t n_waves = (int64_t)gridDim.x * (VRT_BLOCK / VRT_WAVE);
+        const int64_t wave = (int64_t)blockIdx.x * (VRT_BLOCK / VRT_WAVE) + wave_in_block;
+        int64_t per = (count + n_waves - 1) / n_waves;
+        per = (per + 7) & ~(int64_t)7;
+        next = wave * per;
+        range_end = next + per < count ? next + per : count;
+        more = false;
+    }
+
+    Ray r;
+    ray_clear(r);
+    int state = LANE_IDLE;
+    uint32_t n_bad = 0;      // wave-uniform: rays rejected
+    int32_t cnt[C_NLOCAL];   // events of the current ray
+#pragma unroll
+    for (int j = 0; j < C_NLOCAL; j++) cnt[j] = 0;
+    SeenList<false> sl = seen_unused();
+    LkState lk = lk_unused();
+    DG_LANE(dg);
+
+    for (;;) {
+        // ------------------------------------------------------------------ refill idle lanes
+        unsigned long long idle_mask = __ballot(state == LANE_IDLE);
+        while (idle_mask != 0ull && (next < range_end || more)) {
+            if (next >= range_end) {  // take the next chunk (one atomic per wave per chunk)
+                unsigned long long base = 0;
+                if ((threadIdx.x & 63) == 0) base = atomicAdd(P.queue_head, (unsigned long long)chunk);
+                base = wave_first_u64(base);  // (into scalar registers: what is derived from it stays wave-uniform, scalar code)
+                if ((int64_t)base >= count) {
+                    more = false;
+                    break;
+                }
+                next = (int64_t)base;
+                range_end = next + chunk < count ? next + chunk : count;
+            }
+            const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(idle_mask >> 32),
+                                                            __builtin_amdgcn_mbcnt_lo((unsigned)idle_mask, 0u));
+            const int64_t k = next + rank;
+            next += __popcll(idle_mask);
+            bool bad = false;
+            if (state == LANE_IDLE && k < range_end) {
+                const auto& Q = fresh_args(P);
+                const int64_t ray = Q.ray0 + k;
+                // the whole record is fetched at once (one memory round trip), then inspected
+                const CastRecord c = reinterpret_cast<const CastRecord*>(Q.tab.rec)[ray];
+                if (cast_ray_ok(c, Q.lens, C.cs)) {
+                    // init.py:50-59: the caller's doubles are the ray's state
+                    r.px = c.ox; r.py = c.oy; r.pz = c.oz;
+                    r.vx = c.vx; r.vy = c.vy; r.vz = c.vz;
+                    r.life = c.life;
+                    r.step = 0;
+                    r.bounces = 0;
+                    r.energy = 0;
+                    r.color = 0;
+                    // chunk_min = chunk_max = vec3(0, 0, 0), chunk = None (init.py:46-47): see take_ray
+                    r.nm4x = r.nm4y = r.nm4z = (int)0x80000000u;
+                    r.entry = 0;
+                    r.boff = 0;
+                    r.resnaps = 0;
+                    r.off = (uint32_t)k;
+                    r.ndraw = 0;
+                    r.rowi = (uint32_t)ray;
+                    r.d0 = r.d1 = r.d2 = 0.5;
+                    if (3 <= Q.n_draws) {  // the draws of the ray's first rough hit (hit_body asks for the later ones)
+                        const double* row = Q.draws + ray * Q.draw_stride;
+                        r.d0 = row[0];
+                        r.d1 = row[1];
+                        r.d2 = row[2];
+                    }
+#pragma unroll
+                    for (int j = 0; j < C_NLOCAL; j++) cnt[j] = 0;
+                    state = LANE_MARCH;
+                } else {
+                    path_close(Q, (uint32_t)ray, -2);  // rejected: reported, never marched
+                    bad = true;
+                }
+            }
+            n_bad += (uint32_t)__popcll(__ballot(bad));
+            idle_mask = __ballot(state == LANE_IDLE);
+        }
+        if (__ballot(state != LANE_IDLE) == 0ull) break;  // range exhausted and every lane finished
+
+        // ------------------------------------------------------------------ MARCH steps (phase A)
+        int iters = 0;
+        for (;;) {
+            const int n_march = (int)__popcll(__ballot(state == LANE_MARCH));
+            const int n_hit = (int)__popcll(__ballot(state == LANE_HIT));
+            const int n_end = (int)__popcll(__ballot(state >= LANE_ENDED));
+            if (n_march == 0 || n_hit >= P.t_hit || n_end >= P.t_end) break;
+            if (iters >= P.max_iters && n_hit + n_end > 0) break;
+            iters++;
+            if (state == LANE_MARCH) march_step<SPEC, RESMODE, false, 0>(P, C, r, state, cnt, 0ull, lk, sl, dg);
+        }
+        const bool none_marching = __ballot(state == LANE_MARCH) == 0ull;
+        const bool capped = iters >= P.max_iters;
+
+        // ------------------------------------------------------------------ HIT (phase B: init.py:78-116), its record first
+        const bool serve_hit = none_marching || capped || (int)__popcll(__ballot(state == LANE_HIT)) >= P.t_hit;
+        if (serve_hit && state == LANE_HIT) {
+            const auto& Q = fresh_args(P);
+            if (cnt[C_HIT] < Q.max_hits) {  // (ray * max_hits + hit < 2^31: vrt_path_rays)
+                int cx, cy, cz;
+                floor3_i32(r.px, r.py, r.pz, cx, cy, cz);
+                write_hit(Q.hits + ((uint32_t)(Q.ray0 + r.off) * (uint32_t)Q.max_hits + (uint32_t)cnt[C_HIT]), r.step, r.px, r.py, r.pz,
+                          cx, cy, cz, (int)(r.color >> 24));
+            }
+            hit_body<RESMODE, false>(P, C, r, state, cnt, dg);
+        }
+
+        // ------------------------------------------------------------------ ENDED: the count, the unused slots, background, rgba
+        const bool serve_ended = none_marching || capped || (int)__popcll(__ballot(state >= LANE_ENDED)) >= P.t_end ||
+                                 __ballot(state == LANE_MARCH) == 0ull;
+        if (serve_ended && state >= LANE_ENDED) {
+            const auto& Q = fresh_args(P);
+            const int hits = cnt[C_HIT], max_hits = Q.max_hits;
+            path_close(Q, (uint32_t)(Q.ray0 + r.off), state == LANE_ENDED_EXHAUSTED ? -3 : hits);
+            if (state != LANE_ENDED_EXHAUSTED) {
+                if (hits > max_hits) atomicAdd(&S.stats[VRT_S_PATH_TRUNCATED], 1ull);
+                if (hits > 0) atomicAdd(&S.stats[VRT_S_PATH_RECORDS], (unsigned long long)(hits < max_hits ? hits : max_hits));
+            }
+            ended_body<false, true, true>(P, C, r, state, cnt, 0, S.stats);
+            state = LANE_IDLE;
+        }
+    }
+    if ((threadIdx.x & 63) == 0 && n_bad) atomicAdd(&S.stats[VRT_S_CAST_REJECTED], (unsigned long long)n_bad);
+    march_epilogue<false>(P, S);
+}
+
+// ---- pixel_rays_kernel: a frame's primary rays as vrt_cast_ray records (vrt_pixel_rays) -----------------------------------
+// Record k of the launch is the start state first_hit_kernel gives ray slot k * slot_stride: take_ray itself, with the
+// camera in the same LDS words, so the doubles are the frame's.  No voxels are read and no tables built; an unused sample
+// slot gets eight NaNs, which every explicit-ray call rejects.  PERPIX: the ray table holds one record per pixel.
+template <int PERPIX>
+__global__ void __launch_bounds__(VRT_BLOCK) pixel_rays_kernel(MarchParams P) {
+    __shared__ double s_cold[COLD_N];
+    if (threadIdx.x == 0) {
+        for (int j = 0; j < COLD_N; j++) s_cold[j] = 0.0;
+        for (int a = 0; a < 3; a++) s_cold[COLD_POS + a] = P.cam.pos[a];
+        for (int a = 0; a < 4; a++) s_cold[COLD_ROT + a] = P.cam.rot[a];
+        s_cold[COLD_DIST_MIN] = P.st.dist_min;
+    }
+    __syncthreads();
+    MarchCtx C;
+    C.cold = (const lds_f64*)s_cold;
+    C.tile = true;
+    SeenList<false> sl = seen_unused();
+    DG_LANE(dg);
+    uint32_t n_used = 0;  // wave-uniform: records that hold a ray
+    const int64_t rounds = (P.n + (int64_t)gridDim.x * VRT_BLOCK - 1) / ((int64_t)gridDim.x * VRT_BLOCK);
+    for (int64_t i = 0; i < rounds; i++) {
+        const int64_t k = (i * gridDim.x + blockIdx.x) * VRT_BLOCK + threadIdx.x;
+        bool used = false;
+        if (k < P.n) {
+            Ray r;
+            ray_clear(r);
+            used = take_ray<false, false, PERPIX, false, 0, true>(P, C, k * P.slot_stride, r, dg, 0ull, sl);
+            const double nan = __builtin_nan("");
+            CastRecord c;
+            c.ox = used ? r.px : nan; c.oy = used ? r.py : nan; c.oz = used ? r.pz : nan;
+            c.vx = used ? r.vx : nan; c.vy = used ? r.vy : nan; c.vz = used ? r.vz : nan;
+            c.life = used ? r.life : nan;
+            c.reserved = used ? 0.0 : nan;
+            reinterpret_cast<CastRecord*>(fresh_args(P).out_rays)[k] = c;
+        }
+        n_used += (uint32_t)__popcll(__ballot(used));
+    }
+    if ((threadIdx.x & 63) == 0 && n_used) atomicAdd((unsigned long long*)&P.stats[VRT_S_RAYS], (unsigned long long)n_used);
+}
+
+// kernel variant: as launch_shade chooses it, LDS room included; launch_fn, not launch_by_res: the census stays as it is
+static void launch_path(MarchParams P, int grid, int resmode, hipStream_t stream) {
+    P.wt_on = 0;
+    const size_t lds = march_lds(P, false, false);
+#define VRT_PATH(S, R) &path_kernel<S, R>
+    launch_fn(VRT_BY_RES(resmode, VRT_PATH), grid, lds, stream, P);
+#undef VRT_PATH
+}
+
+extern "C" {
+
+int vrt_path_workspace_bytes(int64_t n_rays, int64_t* bytes) { return vrt_shade_workspace_bytes(n_rays, bytes); }
+
+int vrt_path_rays(const vrt_scene* scene, const vrt_settings* st, const vrt_cast_ray* d_rays, int64_t n_rays, double max_life,
+                  const double* d_draws, int32_t n_draws, int32_t max_hits, void* d_workspace, int64_t workspace_bytes,
+                  vrt_hit* d_hits, int32_t* d_counts, uint32_t* d_rgba, uint64_t* d_stats, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    MarchParams P;
+    int rc = fill_scene_params(P, scene, st, nullptr, nullptr, d_stats);  // (every check comes before any HIP call)
+    if (rc != VRT_OK) return rc;
+    if (n_rays < 0 || n_rays >= 4294967295ll || !(max_life > 0.0) || !(max_life <= 0x1p28)) return VRT_ERR_ARG;
+    if (n_draws < 0 || (n_draws > 0 && !d_draws) || !d_workspace) return VRT_ERR_ARG;
+    if (max_hits < 1 || max_hits > 64 || n_rays * max_hits >= (1ll << 31)) return VRT_ERR_ARG;
+    if (n_rays > 0 && (!d_hits || !d_counts || ((uintptr_t)d_hits & 7) != 0 || ((uintptr_t)d_counts & 3) != 0)) return VRT_ERR_ARG;
+    if (n_rays > 0 && (!d_rays || ((uintptr_t)d_rays & 63) != 0)) return VRT_ERR_ARG;
+    int64_t need = 0;
+    vrt_path_workspace_bytes(n_rays, &need);
+    if (workspace_bytes < need) return VRT_ERR_WORKSPACE;
+    unsigned long long* qh = (unsigned long long*)d_workspace;
+    const FrameMemo memo = frame_memo(st, (char*)d_workspace + 256, n_rays > 0);
+    P.pow_global = memo.p;
+    frame_begin(d_stats, qh, n_rays > 0 ? 64 : 0, memo.p, memo.clear, nullptr, stream);
+    const int resmode = res_mode(scene);
+    const bool big = march_big_scene(scene);
+    P.lens = max_life;  // (path_kernel: the bound on a ray's life)
+    P.queue_head = qh;
+    P.tab.rec = reinterpret_cast<RayRecord*>(const_cast<vrt_cast_ray*>(d_rays));
+    P.draws = d_draws;
+    P.n_draws = n_draws;
+    P.draw_stride = n_draws;
+    P.first_draw = 0;
+    P.ray_rgba = d_rgba;
+    P.hits = d_hits;
+    P.path_counts = d_counts;
+    P.max_hits = max_hits;
+    const int64_t per_launch = batch_rays();
+    for (int64_t r0 = 0; r0 < n_rays; r0 += per_launch) {
+        const int64_t n = n_rays - r0 < per_launch ? n_rays - r0 : per_launch;
+        if (r0 > 0) clear_words(qh, 8, stream);
+        P.ray0 = r0;
+        P.n = n;
+        P.chunk = march_chunk(n);
+        march_policy(big, n, P.t_hit, P.t_end, P.max_iters);
+        ProfScope ps(stream, VRT_PROF_MARCH);
+        launch_path(P, march_grid(n), resmode, stream);
+    }
+    HIP_TRY(hipGetLastError());
+    return VRT_OK;
+}
+
+int vrt_pixel_rays(const vrt_scene* scene, const vrt_settings* st, const vrt_camera* cam, const int32_t* d_pixels_xy, int64_t n_px,
+                   const void* d_plan, int64_t n_distinct, const double* d_ray_table, int32_t first_sample_only, vrt_cast_ray* d_rays,
+                   uint64_t* d_stats, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    MarchParams P;
+    int rc = fill_params(P, scene, st, cam, nullptr, d_stats);  // (the range rule of a frame, before any HIP call)
+    if (rc != VRT_OK) return rc;
+    rc = first_hit_params(P, st, d_pixels_xy, n_px, d_plan, n_distinct, d_ray_table, reinterpret_cast<vrt_hit*>(d_rays), 1);
+    if (rc != VRT_OK) return rc;
+    if (((uintptr_t)d_rays & 63) != 0) return VRT_ERR_ARG;  // (what the explicit-ray calls ask of their rays)
+    frame_begin(d_stats, nullptr, 0, nullptr, 0, nullptr, stream);
+    if (n_px == 0) return VRT_OK;
+    const int64_t records = first_sample_only ? n_px : n_px * P.g.smax;
+    P.ray0 = 0;
+    P.n = records;
+    P.slot_stride = first_sample_only ? P.g.smax : 1;
+    P.out_rays = d_rays;
+    const int64_t blocks = grid_for(records);
+    const dim3 grid((unsigned)(blocks < 4096 ? blocks : 4096));
+    if (P.per_pixel) hipLaunchKernelGGL(pixel_rays_kernel<1>, grid, dim3(VRT_BLOCK), 0, stream, P);
+    else hipLaunchKernelGGL(pixel_rays_kernel<0>, grid, dim3(VRT_BLOCK), 0, stream, P);
     HIP_TRY(hipGetLastError());
     return VRT_OK;
 }

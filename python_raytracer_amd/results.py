@@ -75,7 +75,7 @@ class _HitRecords(_LazyStats):
 
     def numpy(self):
         """The records as a numpy structured array (fields step, pos, cell, material)."""
-        return self.records.cpu().numpy().view(np.dtype(nat.HIT_FIELDS))
+        return np.ascontiguousarray(self.records.cpu().numpy()).view(np.dtype(nat.HIT_FIELDS)).reshape(-1)
 
 
 class HitResult(_HitRecords):
@@ -127,6 +127,55 @@ class CastResult(_HitRecords):
         """torch.bool [n]: the ray was rejected on the device (not finite, life > max_life, |vel| > 2**25, or out of
         range: include/vrt.h, vrt_cast_ray) and was not marched."""
         return self.material == nat.HIT_REJECTED
+
+
+class PathResult(_LazyStats):
+    """Device-side outputs of Camera.path_rays: every voxel each explicit ray shaded.  `records` is one flat uint8 buffer of
+    n * max_hits 48-byte vrt_hit records (include/vrt.h), row k the hits of ray k in the order it met them, unused slots
+    marked material -1 with every other field 0 -- DeviceWorld.owners takes the buffer as it is and answers OWNER_NONE for
+    those.  `counts` (int32 [n]) holds ALL hits of a ray, which may exceed max_hits (the row then holds the first max_hits);
+    -2 a rejected ray, -3 one whose draws ran out.  `rgba` (uint32 [n], or None) is packed r | g << 8 | b << 16 | alpha << 24.
+    `stats`: numpy int64[16], copied from the device on first use (a synchronisation): words 0..10 as ShadeResult's, 12
+    completed rays with more hits than max_hits, 13 hit records written for completed rays."""
+
+    def __init__(self, records, counts, rgba, stats_dev, max_hits):
+        self.records = records           # uint8 [n * max_hits * 48]
+        self.counts = counts             # int32 [n]
+        self.rgba = rgba                 # uint32 [n], or None
+        self.max_hits = int(max_hits)
+        self._stats_dev = stats_dev
+
+    def numpy(self):
+        """The records as a numpy structured array [n, max_hits] (fields step, pos, cell, material)."""
+        return self.records.cpu().numpy().view(np.dtype(nat.HIT_FIELDS)).reshape(-1, self.max_hits)
+
+    def truncated_mask(self):
+        """torch.bool [n]: the ray was completed and shaded more voxels than its row holds."""
+        return self.counts > self.max_hits
+
+    def rejected_mask(self):
+        """torch.bool [n]: the ray was rejected on the device (cast_rays's rule) and was not marched."""
+        return self.counts == nat.PATH_REJECTED
+
+    def exhausted_mask(self):
+        """torch.bool [n]: the ray needed more draws than it was given and was not completed: repeat it with a longer row."""
+        return self.counts == nat.PATH_EXHAUSTED
+
+    def hit(self, j):
+        """A CastResult view (no copy) of every ray's j-th record: `material` > 0 where the ray shaded at least j + 1 voxels,
+        -1 where it did not (a rejected ray's material is -1 here too, not -2: see rejected_mask())."""
+        import torch
+        j = int(j)
+        if not 0 <= j < self.max_hits:
+            raise IndexError("hit(%d): the rows hold %d records" % (j, self.max_hits))
+        n = self.records.numel() // (nat.HIT_BYTES * self.max_hits)
+        f64 = self.records.view(torch.float64).view(n, self.max_hits, nat.HIT_BYTES // 8)[:, j]
+        i32 = self.records.view(torch.int32).view(n, self.max_hits, nat.HIT_BYTES // 4)[:, j]
+        out = CastResult.__new__(CastResult)
+        out.records = self.records.view(n, self.max_hits * nat.HIT_BYTES)[:, j * nat.HIT_BYTES:(j + 1) * nat.HIT_BYTES]
+        out.step, out.pos, out.cell, out.material = f64[:, 0], f64[:, 1:4], i32[:, 8:11], i32[:, 11]
+        out._stats_dev = self._stats_dev
+        return out
 
 
 class ShadeResult(_LazyStats):
