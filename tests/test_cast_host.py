@@ -1,22 +1,18 @@
 """Explicit rays without a GPU: the references of tests/test_gpu_cast.py against each other (the Python restatement of the
 reference's loop in tests/cast_ref.py, pinned to the CPU oracle), the C ABI's new symbol and record, what vrt_cast_rays
-refuses before any HIP call, and the compiler's resource report of cast_kernel (the recipe of tests/test_kernel_resources.py)."""
+refuses before any HIP call, and the compiler's resource report of cast_kernel (tests/kernel_report.py)."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import cast_ref as cr
+import kernel_report
 from python_raytracer_amd import _native as nat
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "python_raytracer_amd", "csrc", "vrt_kernels.hip")
-HEADER = os.path.join(ROOT, "include", "vrt.h")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+HEADER = os.path.join(kernel_report.ROOT, "include", "vrt.h")
 
 
 # ---- the restatement against the oracle --------------------------------------------------------------------------------
@@ -86,19 +82,8 @@ def test_cast_rays_rejects_bad_arguments_without_a_device():
 
 # ---- the compiler's resource report ------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def report(tmp_path_factory):
-    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
-        pytest.skip("no hipcc")
-    out = tmp_path_factory.mktemp("res") / "vrt.o"
-    p = subprocess.run([HIPCC, "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-std=c++17", "--cuda-device-only", "-c",
-                        "-Rpass-analysis=kernel-resource-usage", SRC, "-o", str(out)], capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    blocks = {}
-    for b in re.split(r"(?=remark: Function Name: )", p.stderr):
-        m = re.match(r"remark: Function Name: (\S+)", b)
-        if m:
-            blocks[m.group(1)] = {k: int(v) for k, v in re.findall(r"remark:\s+([A-Za-z \[\]/]+): (\d+)", b)}
-    return blocks
+def report():
+    return kernel_report.report()
 
 
 # cast_kernel<SPEC, RESMODE>: the instances the library launches (launch_first_hit's choice)
@@ -112,33 +97,4 @@ def test_cast_kernel_resources(report, spec, res):
     assert r["VGPRs Spill"] == 0 and r["AGPRs"] == 0, r
     assert r["Occupancy [waves/SIMD]"] >= 4 and r["VGPRs"] <= 128, r
     assert r["ScratchSize [bytes/lane]"] <= min(s["ScratchSize [bytes/lane]"] for s in siblings), r
-
-
-def test_first_hit_kernel_keeps_its_figures(report):
-    """first_hit_kernel is pinned: every figure of its twelve instances is the one in profiles/first_hit_kernel_resource_usage.txt,
-    recorded when the pass was added -- but for the moves profiles/shared_handout_kernel_resource_usage.txt records as
-    `before -> after` since (two instances went from 66 to 70 scalar registers when the hand-out became a shared piece):
-    there `before` must be the first file's figure and `after` the compiler's."""
-    def blocks(name):
-        text = open(os.path.join(ROOT, "profiles", name)).read()
-        out = {}
-        for b in re.split(r"(?=Function Name: )", text):
-            m = re.match(r"Function Name: (\S+)", b)
-            if m:
-                out[m.group(1)] = b
-        return out
-
-    pinned = {k: {f: int(v) for f, v in re.findall(r"\n\s+([A-Za-z \[\]/]+): (\d+)", b)}
-              for k, b in blocks("first_hit_kernel_resource_usage.txt").items() if k.startswith("_Z16first_hit_kernel")}
-    assert len(pinned) == 12 and all(len(f) == 8 for f in pinned.values())
-    moved = 0
-    for k, b in blocks("shared_handout_kernel_resource_usage.txt").items():
-        for f, before, after in re.findall(r"\n\s+([A-Za-z \[\]/]+): (\d+) -> (\d+)", b):
-            if k in pinned:
-                assert pinned[k][f] == int(before), (k, f)
-                pinned[k][f] = int(after)
-                moved += 1
-    assert moved == 2
-    for name, figures in pinned.items():
-        assert name in report, name
-        assert {k: report[name][k] for k in figures} == figures, (name, report[name], figures)
+    # (every figure of cast_kernel and first_hit_kernel is pinned with all the others: tests/test_kernel_resources.py)

@@ -216,29 +216,3 @@ def test_edit_record_is_64_bytes():
     assert ctypes.sizeof(nat.VrtEdit) == 64 == nat.EDIT_BYTES
     assert [(f[0], getattr(nat.VrtEdit, f[0]).offset) for f in nat.VrtEdit._fields_] == [
         ("model", 0), ("size", 8), ("lo", 20), ("hi", 32), ("value", 44), ("force", 48), ("pad", 52)]
-
-
-def _edit_kernel_report(text):
-    blocks = {}
-    for b in re.split(r"(?=remark: Function Name: )", text):
-        m = re.match(r"remark: Function Name: (\S+)", b)
-        if m:
-            blocks[m.group(1)] = {k: int(v) for k, v in re.findall(r"remark:\s+([A-Za-z \[\]/]+): (\d+)", b)}
-    return {k: v for k, v in blocks.items() if "edit_models_kernel" in k or "stamp_model_kernel" in k}
-
-
-def test_saved_edit_kernel_resources_are_the_compilers(tmp_path):
-    """profiles/edit_kernel_resource_usage.txt (read by tests/test_gpu_edit.py) holds the two kernels' figures as the compiler
-    gives them for the source in the tree."""
-    import shutil
-    import subprocess
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not (os.path.exists(hipcc) or shutil.which(hipcc)):
-        pytest.skip("no hipcc")
-    p = subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-std=c++17", "--cuda-device-only", "-c",
-                        "-Rpass-analysis=kernel-resource-usage", os.path.join(ROOT, "python_raytracer_amd", "csrc", "vrt_kernels.hip"),
-                        "-o", str(tmp_path / "vrt.o")], capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    now = _edit_kernel_report(p.stderr)
-    saved = _edit_kernel_report(open(os.path.join(ROOT, "profiles", "edit_kernel_resource_usage.txt")).read())
-    assert len(now) == 2 and now == saved

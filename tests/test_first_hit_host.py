@@ -1,20 +1,12 @@
 """The first-hit pass without a GPU: the C ABI's new symbols and record layout, what the entry points refuse before any HIP
-call, and the compiler's resource report of first_hit_kernel (cross-compiled for gfx950: the recipe of
-tests/test_kernel_resources.py)."""
+call, and the compiler's resource report of first_hit_kernel (cross-compiled for gfx950: tests/kernel_report.py)."""
 import ctypes as C
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import kernel_report
 from python_raytracer_amd import _native as nat
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "python_raytracer_amd", "csrc", "vrt_kernels.hip")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 def test_library_exports_the_first_hit_entry_points():
@@ -98,19 +90,8 @@ def test_first_hit_rejects_bad_arguments_without_a_device():
 
 # ---- the compiler's resource report ----------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def report(tmp_path_factory):
-    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
-        pytest.skip("no hipcc")
-    out = tmp_path_factory.mktemp("res") / "vrt.o"
-    p = subprocess.run([HIPCC, "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-std=c++17", "--cuda-device-only", "-c",
-                        "-Rpass-analysis=kernel-resource-usage", SRC, "-o", str(out)], capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    blocks = {}
-    for b in re.split(r"(?=remark: Function Name: )", p.stderr):
-        m = re.match(r"remark: Function Name: (\S+)", b)
-        if m:
-            blocks[m.group(1)] = {k: int(v) for k, v in re.findall(r"remark:\s+([A-Za-z \[\]/]+): (\d+)", b)}
-    return blocks
+def report():
+    return kernel_report.report()
 
 
 # first_hit_kernel<SPEC, RESMODE, PERPIX, VIEWS>: the instances the library launches, and the frame's march_kernel of the same

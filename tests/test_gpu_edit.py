@@ -424,9 +424,9 @@ def test_long_journals_and_lod_sprites_are_copied_anew():
 @gpu
 def test_edit_kernels_use_no_scratch_and_spill_nothing():
     """The compiler's own report for gfx950 (-Rpass-analysis=kernel-resource-usage), saved in
-    profiles/edit_kernel_resource_usage.txt and compared with a fresh compilation by tests/test_edit_host.py."""
-    from test_edit_host import _edit_kernel_report
-    rep = _edit_kernel_report(open(os.path.join(ROOT, "profiles", "edit_kernel_resource_usage.txt")).read())
+    profiles/kernel_resource_usage.txt and compared with a fresh compilation by tests/test_kernel_resources.py."""
+    import kernel_report
+    rep = {k: v for k, v in kernel_report.saved().items() if "edit_models_kernel" in k or "stamp_model_kernel" in k}
     assert sorted(re.sub(r"^_Z\d+", "", k)[:12] for k in rep) == ["edit_models_", "stamp_model_"]
     for name, r in rep.items():
         assert r["ScratchSize [bytes/lane]"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0, (name, r)

@@ -26,7 +26,7 @@ import time
 import numpy as np
 import pytest
 
-import test_kernel_resources as kr
+import kernel_report
 from test_march_variant import ROWS
 
 RETRACE = ('march_kernel<4,2,false,true,0,4,false,false,1>', 'march_kernel<4,2,false,true,0,4,false,false,2>')
@@ -302,7 +302,7 @@ def test_legs_cover_every_selectable_instance():
     """The union of the legs' sets is the table's selectable rows (all but the record / re-trace variant that neither records
     nor re-traces) less EXEMPT, every name is one ROWS knows, and every family is there.  With the per-leg equality of the GPU
     test: every selectable instance was launched and compared with the oracle.  Needs no GPU."""
-    src = open(kr.SRC).read()
+    src = open(kernel_report.SRC).read()
     table = re.findall(r"^    X\((\d), (\w+), (\d), (\w+), (\w+), (\d), (\d), (\w+), (\w+), (\w+), (\d)\)", src, re.M)
     spec = {"VRT_SPEC": "4", "VRT_SPEC_DEEP": "8", "8": "8"}
     selectable = set()

@@ -1,16 +1,12 @@
 """The frame march kernels must keep four waves per SIMD without vector spills: the compiler's own resource report
-(-Rpass-analysis=kernel-resource-usage) of the shipped source, cross-compiled for gfx950 (no GPU needed).  A change that
-pushes a frame kernel over 128 VGPRs costs tens of per cent on the GPU and would otherwise only show up in a bench run."""
-import os
+(-Rpass-analysis=kernel-resource-usage) of the shipped source, cross-compiled for gfx950 (no GPU needed: tests/kernel_report.py).
+A change that pushes a frame kernel over 128 VGPRs costs tens of per cent on the GPU and would otherwise only show up in a
+bench run.  And every figure of every device function is pinned: the report equals profiles/kernel_resource_usage.txt."""
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "python_raytracer_amd", "csrc", "vrt_kernels.hip")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+import kernel_report
 
 # mangled names of the kernels a frame runs at the BASELINE configurations
 # (the last template arguments: W = the look-ahead crosses chunk borders, march_step_w -- the measured variant, VRT_WADDR=1;
@@ -46,19 +42,19 @@ RAYGEN_KERNELS = {
 
 
 @pytest.fixture(scope="module")
-def report(tmp_path_factory):
-    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
-        pytest.skip("no hipcc")
-    out = tmp_path_factory.mktemp("res") / "vrt.o"
-    p = subprocess.run([HIPCC, "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-std=c++17", "--cuda-device-only", "-c",
-                        "-Rpass-analysis=kernel-resource-usage", SRC, "-o", str(out)], capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    blocks = {}
-    for b in re.split(r"(?=remark: Function Name: )", p.stderr):
-        m = re.match(r"remark: Function Name: (\S+)", b)
-        if m:
-            blocks[m.group(1)] = {k: int(v) for k, v in re.findall(r"remark:\s+([A-Za-z \[\]/]+): (\d+)", b)}
-    return blocks
+def report():
+    return kernel_report.report()
+
+
+def test_report_is_the_saved_one(report):
+    """Every device function the compiler reports on -- the same names in the same order of emission -- has the eight figures
+    profiles/kernel_resource_usage.txt holds for it.  A kernel change that moves one on purpose regenerates the file in the
+    same commit (python tests/kernel_report.py --write)."""
+    saved = kernel_report.saved()
+    assert len(saved) == 132 and all(tuple(figs) == kernel_report.FIGURES for figs in saved.values())
+    assert list(report) == list(saved)
+    for name, figs in saved.items():
+        assert report[name] == figs, (name, report[name], figs)
 
 
 @pytest.mark.parametrize("name", sorted(FRAME_KERNELS))

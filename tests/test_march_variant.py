@@ -8,6 +8,7 @@ no kernel exists for, which the old launcher ran through another kernel's branch
 import ctypes as C
 import re
 
+import kernel_report
 import test_kernel_resources as kr
 from python_raytracer_amd import _native as nat
 
@@ -127,7 +128,7 @@ def test_every_row_runs_the_recorded_instance():
 def test_rows_cover_every_instance_a_launch_can_select():
     """Every march_kernel / march_pool_kernel instance of the library's table but the one no launch selects, and the
     kernels tests/test_kernel_resources.py names for the shipped operating points."""
-    src = open(kr.SRC).read()
+    src = open(kernel_report.SRC).read()
     table = re.findall(r"^    X\((\d), (\w+), (\d), (\w+), (\w+), (\d), (\d), (\w+), (\w+), (\w+), (\d)\)", src, re.M)
     spec = {"VRT_SPEC": "4", "VRT_SPEC_DEEP": "8", "8": "8"}
     shipped = set()
@@ -155,7 +156,7 @@ def test_march_variant_diagnostic_is_exported_and_checks_its_arguments():
     """Outside include/vrt.h and _native.EXPORTS (no ABI change), host memory only."""
     L = nat.lib()
     assert "vrt_diag_march_variant" not in nat.EXPORTS
-    assert "vrt_diag_march_variant" not in open(kr.SRC.replace("python_raytracer_amd/csrc/vrt_kernels.hip", "include/vrt.h")).read()
+    assert "vrt_diag_march_variant" not in open(kernel_report.SRC.replace("python_raytracer_amd/csrc/vrt_kernels.hip", "include/vrt.h")).read()
     n = len(nat.VARIANT_INPUTS)
     words = (C.c_int32 * n)(*[nat.VARIANT_DEFAULTS[k] for k in nat.VARIANT_INPUTS])
     name, eff = C.create_string_buffer(128), (C.c_int32 * 3)(-7, -7, -7)
@@ -198,7 +199,7 @@ def test_launch_census_is_exported_and_checks_its_arguments():
     """Outside include/vrt.h and _native.EXPORTS (no ABI change); callable without a GPU; a refusal writes nothing."""
     L = nat.lib()
     assert "vrt_diag_launch_census" not in nat.EXPORTS and L.vrt_abi_version() == 9
-    assert "vrt_diag_launch_census" not in open(kr.SRC.replace("python_raytracer_amd/csrc/vrt_kernels.hip", "include/vrt.h")).read()
+    assert "vrt_diag_launch_census" not in open(kernel_report.SRC.replace("python_raytracer_amd/csrc/vrt_kernels.hip", "include/vrt.h")).read()
     n, first, count = census_row(L, 0)
     assert n == 74 + len(BY_RES_NAMES) and first == 'march_kernel<4,2,true,false,0,4,false,false,0>' and count >= 0
     name, cnt = C.create_string_buffer(b"?" * 127, 128), C.c_int64(-7)
@@ -215,7 +216,7 @@ def test_launch_census_rows_are_the_table_and_the_by_resolution_instances():
     L = nat.lib()
     n = census_row(L, 0)[0]
     names = [census_row(L, row)[1] for row in range(n)]
-    src = open(kr.SRC).read()
+    src = open(kernel_report.SRC).read()
     table = re.findall(r"^    X\((\d), (\w+), (\d), (\w+), (\w+), (\d), (\d), (\w+), (\w+), (\w+), (\d)\)", src, re.M)
     assert len(names) == len(set(names)) == len(table) + len(BY_RES_NAMES)
     march, by_res = names[:len(table)], names[len(table):]

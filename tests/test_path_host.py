@@ -1,24 +1,20 @@
 """Hit paths of explicit rays without a GPU: tests/path_ref.py's restatement against the oracle-derived records of
 shade_ref's six ray sets, the preconditions of the cases tests/test_gpu_paths.py runs (asserted on the reference), the C
 ABI's new symbols, what vrt_path_rays and vrt_pixel_rays refuse before any HIP call, and the compiler's resource report of
-path_kernel (the recipe of tests/test_shade_host.py)."""
+path_kernel (tests/kernel_report.py)."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import kernel_report
 import path_ref as pr
 import shade_ref as sr
 from python_raytracer_amd import _native as nat
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "python_raytracer_amd", "csrc", "vrt_kernels.hip")
-HEADER = os.path.join(ROOT, "include", "vrt.h")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+HEADER = os.path.join(kernel_report.ROOT, "include", "vrt.h")
 ALL_SETS = ["default_mb2", "default_mb8", "default_scaled_nobg", "synth64_mb4", "hand", "big_table"]
 
 
@@ -166,19 +162,8 @@ def test_pixel_rays_rejects_bad_arguments_without_a_device():
 
 # ---- 3. the compiler's resource report ---------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def report(tmp_path_factory):
-    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
-        pytest.skip("no hipcc")
-    out = tmp_path_factory.mktemp("res") / "vrt.o"
-    p = subprocess.run([HIPCC, "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-std=c++17", "--cuda-device-only", "-c",
-                        "-Rpass-analysis=kernel-resource-usage", SRC, "-o", str(out)], capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    blocks = {}
-    for b in re.split(r"(?=remark: Function Name: )", p.stderr):
-        m = re.match(r"remark: Function Name: (\S+)", b)
-        if m:
-            blocks[m.group(1)] = {k: int(v) for k, v in re.findall(r"remark:\s+([A-Za-z \[\]/]+): (\d+)", b)}
-    return blocks
+def report():
+    return kernel_report.report()
 
 
 def path_name(spec, res):
@@ -195,16 +180,4 @@ def test_path_kernel_resources(report, spec, res):
     assert r["VGPRs Spill"] == 0 and r["ScratchSize [bytes/lane]"] <= 16, r
     if res == 2:
         assert report["_Z12shade_kernelILi4ELi2ELb0EEv11MarchParams"]["VGPRs"] == 128      # the sibling has none to spare either
-
-
-def test_saved_report_is_the_compilers(report):
-    """profiles/path_kernel_resource_usage.txt holds the new kernels' figures as the compiler gives them."""
-    text = open(os.path.join(ROOT, "profiles", "path_kernel_resource_usage.txt")).read()
-    saved = {}
-    for b in re.split(r"(?=Function Name: )", text):
-        m = re.match(r"Function Name: (\S+)", b)
-        if m:
-            saved[m.group(1)] = {f: int(v) for f, v in re.findall(r"\n\s+([A-Za-z \[\]/]+): (\d+)", b)}
-    assert sorted(saved) == sorted(k for k in report if k.startswith(("_Z11path_kernel", "_Z17pixel_rays_kernel"))) and len(saved) == 5
-    for name, figs in saved.items():
-        assert len(figs) == 8 and {k: report[name][k] for k in figs} == figs, (name, report[name], figs)
+    # (every figure of path_kernel and pixel_rays_kernel is pinned with all the others: tests/test_kernel_resources.py)

@@ -1,22 +1,18 @@
 """Shaded explicit rays without a GPU: that the ray sets of tests/test_gpu_shade.py are not vacuous, the Python restatement
 of Camera.trace's loop in tests/shade_ref.py against the CPU oracle, the C ABI's new symbols, what vrt_shade_rays refuses
-before any HIP call, and the compiler's resource report of shade_kernel (the recipe of tests/test_kernel_resources.py)."""
+before any HIP call, and the compiler's resource report of shade_kernel (tests/kernel_report.py)."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import kernel_report
 import shade_ref as sr
 from python_raytracer_amd import _native as nat
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "python_raytracer_amd", "csrc", "vrt_kernels.hip")
-HEADER = os.path.join(ROOT, "include", "vrt.h")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+HEADER = os.path.join(kernel_report.ROOT, "include", "vrt.h")
 ALL_SETS = ["default_mb2", "default_mb8", "default_scaled_nobg", "synth64_mb4", "hand", "big_table"]
 
 
@@ -148,19 +144,8 @@ def test_shade_rays_rejects_bad_arguments_without_a_device():
 
 # ---- 4. the compiler's resource report ---------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def report(tmp_path_factory):
-    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
-        pytest.skip("no hipcc")
-    out = tmp_path_factory.mktemp("res") / "vrt.o"
-    p = subprocess.run([HIPCC, "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-std=c++17", "--cuda-device-only", "-c",
-                        "-Rpass-analysis=kernel-resource-usage", SRC, "-o", str(out)], capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    blocks = {}
-    for b in re.split(r"(?=remark: Function Name: )", p.stderr):
-        m = re.match(r"remark: Function Name: (\S+)", b)
-        if m:
-            blocks[m.group(1)] = {k: int(v) for k, v in re.findall(r"remark:\s+([A-Za-z \[\]/]+): (\d+)", b)}
-    return blocks
+def report():
+    return kernel_report.report()
 
 
 def shade_name(spec, res, record):
@@ -185,16 +170,4 @@ def test_shade_kernel_resources(report, spec, res, record):
         for f in ("TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "SGPRs Spill", "VGPRs Spill", "LDS Size [bytes/block]"):
             assert r[f] <= m[f], (f, r, m)
         assert r["Occupancy [waves/SIMD]"] >= m["Occupancy [waves/SIMD]"], (r, m)
-
-
-def test_saved_report_is_the_compilers(report):
-    """profiles/shade_kernel_resource_usage.txt holds the six instances' figures as the compiler gives them."""
-    text = open(os.path.join(ROOT, "profiles", "shade_kernel_resource_usage.txt")).read()
-    saved = {}
-    for b in re.split(r"(?=Function Name: )", text):
-        m = re.match(r"Function Name: (\S+)", b)
-        if m:
-            saved[m.group(1)] = {f: int(v) for f, v in re.findall(r"\n\s+([A-Za-z \[\]/]+): (\d+)", b)}
-    assert len(saved) == 6
-    for name, figs in saved.items():
-        assert len(figs) == 8 and {k: report[name][k] for k in figs} == figs, (name, report[name], figs)
+    # (every figure of the six instances is pinned with all the others: tests/test_kernel_resources.py)
