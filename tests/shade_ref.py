@@ -16,14 +16,17 @@ import oracle_lib as ol
 
 RAY_DTYPE = ol.RAY_DTYPE
 PIXEL = cr.PIXEL
-N_DRAWS = 64          # draws per row of the oracle sets (the most a ray of them consumes is asserted below it)
+N_DRAWS = 64          # draws per row of the six ordinary sets (the most a ray of them consumes is asserted below it)
 C_LOOKUP, C_NBR, C_RESNAP, C_CGET, C_HIT, C_DRAW, C_ADV, C_BROKE = range(8)
 
 
-def ray_settings(chunk_size, dist_min, dist_max, max_bounces, max_light=1.0):
-    return ol.make_settings(width=2, height=2, samples=1, chunk_size=chunk_size, dof=0.0, lod_samples=0.0, lod_random=0.0,
-                            lod_edge=0.0, max_bounces=float(max_bounces), max_light=float(max_light), dist_min=dist_min,
-                            dist_max=dist_max)
+def ray_settings(chunk_size, dist_min, dist_max, max_bounces, max_light=1.0, **extra):
+    """extra: settings of the oracle's per-ray block that a set changes (falloff, shutter, lod_bounces); the window and the
+    ray generation (width, height, samples, dof, lod_samples, lod_random, lod_edge) stay what makes pixel (1, 1) the ray."""
+    assert set(extra) <= {"falloff", "shutter", "lod_bounces"}, extra
+    return ol.make_settings(**dict(dict(width=2, height=2, samples=1, chunk_size=chunk_size, dof=0.0, lod_samples=0.0,
+                                        lod_random=0.0, lod_edge=0.0, max_bounces=float(max_bounces), max_light=float(max_light),
+                                        dist_min=dist_min, dist_max=dist_max), **extra))
 
 
 def shade_settings(chunk_size, max_bounces, max_light=1.0, **kw):
@@ -64,10 +67,14 @@ def marker(s):
     return rec[0]
 
 
-def oracle_shade(sc, cam_pos, quats, lives, nonces, max_bounces, has_background, max_light=1.0, dist_min=0):
-    """One oracle call per ray.  Returns (origins [n, 3], vels [n, 3], lives [n], draws [n, N_DRAWS], expected vrt_ray records
+def oracle_shade(sc, cam_pos, quats, lives, nonces, max_bounces, has_background, max_light=1.0, dist_min=0, n_draws=N_DRAWS,
+                 **extra):
+    """One oracle call per ray.  Returns (origins [n, 3], vels [n, 3], lives [n], draws [n, n_draws], expected vrt_ray records
     [n], the rays' traversed lists): the rays as shade_rays takes them and what it must give.  The oracle's record becomes
-    the expected one with x = y = s = 0, detail = 1 and the draw counter less the lod_random draw."""
+    the expected one with x = y = s = 0, detail = 1 and the draw counter less the lod_random draw.
+    n_draws: the width of a row; None sizes it from the oracle's own draw counters -- the most draws a ray of the set
+    consumes in its loop, at least 1.  Either way no ray may need more than its row holds (asserted).
+    extra: what ray_settings takes besides (falloff, shutter, lod_bounces)."""
     cam_pos = np.asarray(cam_pos, np.float64).reshape(-1, 3)
     quats = np.asarray(quats, np.float64).reshape(-1, 4)
     lives = np.asarray(lives, np.float64).reshape(-1)
@@ -75,11 +82,10 @@ def oracle_shade(sc, cam_pos, quats, lives, nonces, max_bounces, has_background,
     vels = cr.vec_forward(quats)
     origins = cam_pos + vels * float(dist_min)
     out_lives = (float(dist_min) + lives) - float(dist_min)      # init.py:56 with detail = 1
-    draws = np.zeros((n, N_DRAWS))
     exp = np.zeros(n, RAY_DTYPE)
     trav = []
     for k in range(n):
-        st = ray_settings(sc.chunk_size, float(dist_min), float(dist_min) + float(lives[k]), max_bounces, max_light)
+        st = ray_settings(sc.chunk_size, float(dist_min), float(dist_min) + float(lives[k]), max_bounces, max_light, **extra)
         o = ol.render(sc, st, cam_pos[k], quats[k], st["fov"] * np.pi / 8, PIXEL, libm=ol.LIBM_PORTABLE,
                       has_background=has_background, seed_nonce=int(nonces[k]), want_traversed=True, trav_cap=4096)
         assert len(o["rays"]) == 1
@@ -89,14 +95,20 @@ def oracle_shade(sc, cam_pos, quats, lives, nonces, max_bounces, has_background,
             assert r["step"] >= r["life"] and r["bounces"] == 0
             assert np.array_equal(r["vel"].view(np.uint64), vels[k].view(np.uint64)), (k, r["vel"], vels[k])
             assert r["life"] == out_lives[k], (k, r["life"], out_lives[k])
-        assert 1 <= int(r["counters"][C_DRAW]) <= N_DRAWS        # the lod_random draw, then the loop's
+        assert 1 <= int(r["counters"][C_DRAW])                   # the lod_random draw, then the loop's
         r["counters"][C_DRAW] -= 1
         r["x"] = r["y"] = r["s"] = 0
         r["detail"] = 1.0
         exp[k] = r
         assert int(r["ntrav"]) == len(o["traversed"])
         trav.append(np.asarray(o["traversed"], np.int64).reshape(-1, 3))
-        draws[k] = ol.rng_draws(3 + int(nonces[k]), 1 + N_DRAWS)[1:]
+    most = int(exp["counters"][:, C_DRAW].max(initial=0))
+    if n_draws is None:
+        n_draws = max(1, most)
+    assert most <= n_draws, (most, n_draws)                      # no ray runs out of draws
+    draws = np.zeros((n, n_draws))
+    for k in range(n):
+        draws[k] = ol.rng_draws(3 + int(nonces[k]), 1 + n_draws)[1:]
     return origins, vels, out_lives, draws, exp, trav
 
 
