@@ -424,13 +424,22 @@ class Camera:
         if pixels is not None:
             return self.upload_pixels(pixels)
         plist = self._settings().pixels[thread]
-        key = (thread, id(plist), len(plist))
-        hit = self._pixel_cache.get(thread)
-        if hit is None or hit[0] != key:
+        dp = self._cached_pixels(self._pixel_cache.get(thread), plist)
+        if dp is None:
             arr = plist.array if hasattr(plist, "array") else np.asarray(list(plist), np.int32).reshape(-1, 2)
-            hit = (key, self.upload_pixels(arr))
-            self._pixel_cache[thread] = hit
-        return hit[1]
+            dp = self.upload_pixels(arr)
+            self._pixel_cache[thread] = (plist, dp)
+        return dp
+
+    @staticmethod
+    def _cached_pixels(entry, plist):
+        """The DevicePixels of a _pixel_cache entry (the list it was uploaded from, the upload) if `plist` is that very
+        list, unchanged in length; else None.  The entry holds the list itself: finalize_settings replaces
+        settings.pixels, and an id() kept without the object can come back for a new list of the same length (a 64 x 16
+        window resized to 16 x 64), whose frame would then be rendered from the old window's pixels."""
+        if entry is None or entry[0] is not plist or len(entry[1].array) != len(plist):
+            return None
+        return entry[1]
 
     def _plan_for(self, dp, st):
         """Build (once per pixel list and sample settings) the tile plan of `dp`."""
@@ -453,6 +462,7 @@ class Camera:
         hdr = plan[:64].cpu().numpy().view(np.uint64)
         if int(hdr[0]) != nat.PLAN_MAGIC or int(hdr[1]) != n_px:
             raise nat.VrtError("tile plan header is corrupt")
+        self._retire_table(dp, dp.plan)   # (frames on other streams that read the cached tables read the old plan too)
         dp.plan, dp.plan_key, dp.n_distinct = plan, key, int(hdr[3])
         dp.full_frame = bool(hdr[6])   # the list is the whole window (in the reference's x-major order): the plan's own check
         del scratch
@@ -575,7 +585,9 @@ class Camera:
                want_traversed=True, seed_nonce=None, check=True):
         """Run Camera.tile's pixel loop (reference init.py:126-150) on the GPU for settings.pixels[thread] (or an
         explicit [n, 2] pixel array).  Returns a RenderResult holding device tensors; nothing is copied to the
-        host except the 16-word statistics block (when `check`)."""
+        host except the 16-word statistics block (when `check`).
+        A captured graph holds the raw pointers of the plan and the cached tables it was captured with: replaying it after a
+        change that rebuilds them (the lens, the window, the sample or distance settings) is not supported -- capture again."""
         torch = self._torch
         L = nat.lib()
         dp, st, csc, smax, n_px = self._frame_setup(thread, pixels, seed_nonce)

@@ -247,6 +247,39 @@ class PackedScene:
         sc.resident = True
         return sc
 
+    def refresh(self, materials):
+        """After the voxels of a resident scene were rewritten in place (DeviceWorld.update): take the material rows
+        ([n, 7]) as they are now and build again what was derived from the voxels -- the occupancy words the VRT_LOOKUP=1|2
+        variants of the march read in place of the bytes."""
+        self.set_materials(materials)
+        t = self.device_tensors
+        if t is not None and want_occupancy():
+            t["occupancy"] = build_occupancy(t["voxels"], int(self.n_slots) * self.chunk_size ** 3, t.get("occupancy"))
+
+    def set_materials(self, materials):
+        """Replace the material rows ([n, 7]) of a scene: the host rows and, for a resident scene, their device copy, which
+        cameras read at every frame.  An equal number of rows is copied over the old ones in place; a block that is replaced
+        is kept for as long as the scene lives (at most 255 small blocks), because a frame in flight on another stream may
+        still read it and the allocator would hand a freed one out again."""
+        mats = np.zeros((len(materials), 8), np.float64)
+        mats[:, :7] = np.asarray(materials, np.float64).reshape(-1, 7)
+        if len(mats) > 255:
+            raise ValueError("at most 255 materials (u8 voxel ids)")
+        if mats.shape == self.materials.shape and np.array_equal(mats, self.materials):
+            return
+        grew = mats.shape != self.materials.shape
+        self.materials = mats
+        if self.device_tensors is not None:
+            import torch
+            old = self.device_tensors["materials"]
+            flat = torch.from_numpy(mats.reshape(-1))
+            if not grew and old.numel() == flat.numel():
+                old.copy_(flat)
+            else:
+                self._retired_materials = getattr(self, "_retired_materials", []) + [old]
+                self.device_tensors["materials"] = flat.to(old.device) if mats.size else \
+                    torch.zeros(8, dtype=torch.float64, device=old.device)
+
     def to(self, device):
         import torch
         if getattr(self, "resident", False):

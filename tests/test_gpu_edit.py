@@ -431,3 +431,55 @@ def test_edit_kernels_use_no_scratch_and_spill_nothing():
     for name, r in rep.items():
         assert r["ScratchSize [bytes/lane]"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0, (name, r)
         assert r["AGPRs"] == 0 and r["LDS Size [bytes/block]"] == 0 and r["Occupancy [waves/SIMD]"] == 8, (name, r)
+
+
+# ---- 11. the kept scene under the occupancy lookups ------------------------------------------------------------------------
+def lookup_leg():
+    """(a child process of the test below, VRT_LOOKUP set: the variable is read once per process)  The first nine ticks of
+    script B (tests/sequences.py: moves, turns, a hide and edits with and without redraw, all incremental) on one DeviceWorld
+    whose scene one Camera was given once.  After every update the scene is still that object, its occupancy words are those
+    of the voxels as they are now -- bit b of word w: voxel byte 64 w + b holds a material -- and the frame of the camera
+    that still holds it is the oracle's over the host build."""
+    import oracle_lib as ol
+    import sequences as sq
+    from gpu_util import frame_equals_oracle, settings_store
+    from python_raytracer_amd import Camera
+    from python_raytracer_amd.scene import material_row
+    S = sq.ScriptB()
+    cs = S.cs
+    st = ol.make_settings(**sq.SETTINGS_B)
+    dw = DeviceWorld(cs)
+    cam = Camera(settings=settings_store(st))
+    cam.rot, cam.lens = quaternion(*sq.CAM_ROT_B), st["fov"] * np.pi / 8
+    held, changed = None, 0
+    for k in range(9):
+        exp = S.run(k)
+        ps, rebuilt = dw.update(S.objs)
+        S.done()
+        assert rebuilt == exp["chunks"] and bool(exp["full"]) == (k == 0)
+        if k == 0:
+            cam.set_world_scene(ps)
+            held, before = ps, None
+        assert ps is held
+        vox = dw._voxels.cpu().numpy()
+        want = np.packbits(vox.reshape(-1, 64) != 0, axis=1, bitorder="little").view(np.uint64).reshape(-1)
+        occ = ps.device_tensors["occupancy"].cpu().numpy().view(np.uint64)
+        assert np.array_equal(occ[:len(want)], want), k
+        changed += before is not None and not np.array_equal(before, want)
+        before = want
+        cam.pos = vec3(*sq.cam_pos_b(k))
+        grid, present = _merge_world(dw, cs)
+        rows = np.array([material_row(m)[:7] for m in dw.materials], np.float64).reshape(-1, 7)
+        scene = ol.Scene(dw.origin, dw.dims, cs, present, np.ones_like(present), grid, rows)
+        frame_equals_oracle(cam.render(0, want_ray_rgba=True), sq.render_b(k, scene), cs)
+    assert changed >= 6                                   # (the words really had to change under the camera)
+    print("LOOKUP_LEG ok", os.environ["VRT_LOOKUP"])
+
+
+@gpu
+def test_incremental_updates_refresh_the_occupancy_words_of_the_kept_scene():
+    """DeviceWorld.update keeps its scene object across incremental updates; with VRT_LOOKUP=1|2 the march reads the scene's
+    occupancy words in place of the voxel bytes, so they have to follow every update (lookup_leg, one child per variant)."""
+    from gpu_util import run_children
+    lines = run_children("import test_gpu_edit as t; t.lookup_leg()", [{"VRT_LOOKUP": "1"}, {"VRT_LOOKUP": "2"}], "LOOKUP_LEG")
+    assert [l[1:] for l in lines] == [["ok", "1"], ["ok", "2"]]

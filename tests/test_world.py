@@ -251,8 +251,13 @@ def _merge_world(dw, cs):
     origin, dims = np.asarray(dw.origin, np.int64), np.asarray(dw.dims, np.int64)
     grid = np.zeros(tuple(dims * cs), np.uint8)
     if w.grid.any():
+        # (build_world's own box counts an object's maxs as inside: where a box ends on a chunk border it is a layer of empty
+        # chunks larger than the box an incremental update keeps -- only what the two share is copied, and it is everything)
         a = np.asarray(w.origin, np.int64) - origin
-        grid[a[0]:a[0] + w.grid.shape[0], a[1]:a[1] + w.grid.shape[1], a[2]:a[2] + w.grid.shape[2]] = w.grid
+        lo, hi = np.maximum(a, 0), np.minimum(a + w.grid.shape, grid.shape)
+        part = w.grid[tuple(slice(int(l - o), int(h - o)) for l, h, o in zip(lo, hi, a))]
+        assert int((part != 0).sum()) == int((w.grid != 0).sum())
+        grid[tuple(slice(int(l), int(h)) for l, h in zip(lo, hi))] = part
     # build_world numbers materials in first-use order of ITS object order; map them onto the device's ids
     remap = np.zeros(256, np.uint8)
     for k, m in enumerate(w.materials):
