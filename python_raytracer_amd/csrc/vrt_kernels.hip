@@ -1645,7 +1645,11 @@ __device__ __forceinline__ bool take_ray_views(const MarchParams& P, const March
 
 // MARCH: phase A of the reference loop (init.py:66-77, 114-116) for a lane in LANE_MARCH -- loop condition, chunk
 // re-snap, the voxel of this position and speculatively of the next SPEC - 1, advance.  Leaves the lane in LANE_MARCH,
-// LANE_HIT (a voxel was found: its material sits in the colour word's top byte) or LANE_ENDED.
+// LANE_HIT (a voxel was found: its material sits in the colour word's top byte) or LANE_ENDED.  The loop condition is
+// tested twice: at the top for a ray that was born dead (take_ray hands out rays with life <= 0: detail 0), and after
+// the advance for the iteration that would follow -- neither r.step nor r.life changes between the bottom of one
+// iteration and the top of the next, in a lane or in a pool slot, so that is the reference's decision made one march
+// execution sooner (config 3: one lane-step in six went into finding a dead ray dead; profiles/life_end_ab.md).
 #ifndef VRT_FRESH_MARCH
 #define VRT_FRESH_MARCH 0
 #endif
@@ -1942,7 +1946,11 @@ __device__ __forceinline__ void march_step(const MarchParams& P, const MarchCtx&
                 DG_BRICK();
             }
         }
-        if (found) state = LANE_HIT;
+        // the loop condition of the next iteration (init.py:66) is decided here, where the advance has just made its
+        // operands: a ray whose life this step used up takes no lane of another march execution to find that out.  A
+        // found voxel was found at a position the condition allowed: the ray is alive, whatever r.step says now.
+        // (selects, no branch: see hit_body)
+        state = found ? LANE_HIT : (r.step < r.life ? LANE_MARCH : LANE_ENDED);
     } else {  // void skip (init.py:114)
         VRT_MARK("m_void");
         if (DEFER) resnap_finish<DEFER == 2>(Q, C, pend, 0u, wmin_key);
@@ -1960,6 +1968,7 @@ __device__ __forceinline__ void march_step(const MarchParams& P, const MarchCtx&
         r.pz += r.vz * stepsize;
         DG_BRICK();
         cnt[C_ADV]++;
+        state = r.step < r.life ? LANE_MARCH : LANE_ENDED;  // (init.py:66 for the next iteration, as above)
     }
 }
 
@@ -2154,14 +2163,13 @@ __device__ __forceinline__ void march_step_w(const MarchParams& P, const MarchCt
     advance_to(h);
     cnt[C_LOOKUP] += h + (found ? 1 : 0);
     cnt[C_ADV] += h;
-    if (found) {
-        r.color |= id << 24;
-        state = LANE_HIT;
-    }
+    if (found) r.color |= id << 24;
+    state = found ? LANE_HIT : (r.step < r.life ? LANE_MARCH : LANE_ENDED);  // (init.py:66 for the next iteration: see march_step)
 }
 
 // HIT: phase B of the reference loop (init.py:78-116) for a lane in LANE_HIT -- lib.material, the termination tests,
-// the reflection from the three neighbour voxels, the advance.  Leaves the lane in LANE_MARCH or one of the ENDED states.
+// the reflection from the three neighbour voxels, the advance.  Leaves the lane in LANE_MARCH or one of the ENDED states
+// (LANE_ENDED itself when the advance uses up what the hit left of the ray's life: see march_step).
 // LIST (a re-trace launch) with P.prefix_draws > 0: the frame's march counted this ray's events into its lanes' totals
 // up to the hit at which a P.prefix_draws-wide row ran out (march_pool_kernel keeps no per-ray counts); the re-trace
 // walks through the same hit with the same counts and takes them off again there.
@@ -2340,7 +2348,9 @@ __device__ __forceinline__ void hit_body(const MarchParams& P, const MarchCtx& C
         r.pz += r.vz * stepd;
         DG_BRICK();
         cnt[C_ADV]++;
-        state = LANE_MARCH;
+        // the loop's exit (init.py:66), not its `break`: a ray whose shrunken life this advance used up is a plain
+        // LANE_ENDED -- `broke` stays the reference's -- and waits for the ENDED body from here instead of from a march step
+        state = r.step < r.life ? LANE_MARCH : LANE_ENDED;
     }
 }
 

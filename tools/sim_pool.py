@@ -6,6 +6,7 @@ body it executes whatever the number of active lanes.
 
     python tools/sim_pool.py [c3|c5]
     python tools/sim_pool.py passes [c3|c5]     march_pool_kernel's shipped pass policy and its fused passes (VRT_POOL_FUSE)
+    python tools/sim_pool.py passes [c3|c5] --early-end    ... with a ray ENDED by the step that uses up its life
 """
 import random
 import sys
@@ -254,14 +255,31 @@ def private_pool(c, rng, parked=48, n_rays=200000, t_hit=56, t_end=56, swap_min=
     return cost / done, out
 
 
-def shipped_pool(c, rng, fuse=0, slots=48, n_rays=200000, t_hit=40, t_end=60, swap_min=8, refill_min=8, keep=40, max_iters=3):
+def early_end_rates(c):
+    """The chain's rates when the loop condition is decided at the end of the step that uses up the ray's life (march_step,
+    hit_body: LANE_ENDED straight after the advance) instead of by an iteration of its own.  The measured rates are per march
+    iteration, "end" iterations included: from MARCH a ray comes back to MARCH with rho0 = p_hit (1 - p_break) + 1 - p_hit -
+    p_end, so it spends N = 1 / (1 - rho0) iterations, N (1 - p_end) of them on a step that does something.  Of those steps
+    a = p_hit / (1 - p_end) find a voxel.  A ray that goes on after a step or a hit is dead with probability x, and x is what
+    leaves the number of working steps per ray where it was: (1 - x)(1 - a p_break) = 1 - 1 / (N (1 - p_end)).  A fresh ray is
+    alive.  Returns (a, x); config 3: 0.427, 0.218."""
+    rho0 = c["p_hit"] * (1 - c["p_break"]) + 1 - c["p_hit"] - c["p_end"]
+    work = (1 - c["p_end"]) / (1 - rho0)
+    a = c["p_hit"] / (1 - c["p_end"])
+    return a, 1 - (1 - 1 / work) / (1 - a * c["p_break"])
+
+
+def shipped_pool(c, rng, fuse=0, slots=48, n_rays=200000, t_hit=40, t_end=60, swap_min=8, refill_min=8, keep=40, max_iters=3,
+                 early_end=False):
     """march_pool_kernel's pass loop as shipped (python_raytracer_amd/csrc/vrt_kernels.hip): one target per pass -- HIT once
     t_hit rays wait anywhere in the wave's 64 lanes + `slots` parked places, ENDED (+ refill) once t_end do, else MARCH --,
     the exchange that brings rays of the target's state into the lanes (or parks waiting rays in free slots for fresh ones),
     then the bodies in source order.  fuse: -DVRT_POOL_FUSE's bits -- 1: an ENDED pass enters the march loop after its refill
     once `keep` lanes march; 2: the HIT body runs before the march loop and a HIT pass enters it under the same rule.
-    Without rays left to hand out every pass runs all three bodies (tail mode).  Counts, not costs: passes, executions of each
-    body and the lanes they find."""
+    Without rays left to hand out every pass runs all three bodies (tail mode).  early_end: a ray whose life a march step or
+    the HIT body's advance used up is ENDED at the end of that step (early_end_rates) instead of marching once more to find
+    out.  Counts, not costs: passes, executions of each body and the lanes they find."""
+    a_hit, x_dead = early_end_rates(c) if early_end else (0.0, 0.0)
     lanes = [None] * 64      # a lane's state, or None
     park = []                # states of the parked rays
     done = issued = passes = 0
@@ -269,10 +287,14 @@ def shipped_pool(c, rng, fuse=0, slots=48, n_rays=200000, t_hit=40, t_end=60, sw
     lane_sum = {"march": 0, "hit": 0, "end": 0, "refill": 0, "xchg": 0}
 
     def hit_body(st):
-        return E if rng.random() < c["p_break"] else M
+        if rng.random() < c["p_break"]:
+            return E
+        return E if early_end and rng.random() < x_dead else M
 
     def march_body(st):
         u = rng.random()
+        if early_end:
+            return H if u < a_hit else (E if rng.random() < x_dead else M)
         return H if u < c["p_hit"] else (E if u < c["p_hit"] + c["p_end"] else M)
 
     def run(name, state, body):
@@ -352,14 +374,16 @@ def shipped_pool(c, rng, fuse=0, slots=48, n_rays=200000, t_hit=40, t_end=60, sw
     return passes * 64 / done, {k: execs[k] * 64 / done for k in execs}, out
 
 
-def passes_table(name):
+def passes_table(name, early_end=False):
     c = CFG[name]
     pol = dict(c3=(40, 60, 8, 8, 40, 3), c5=(48, 32, 4, 8, 40, 5))[name]   # pool_policy's defaults
     base = None
-    print("%s, shipped knobs %s, 48 slots; per ray x 64" % (name, " / ".join(str(v) for v in pol)))
+    print("%s, shipped knobs %s, 48 slots; per ray x 64%s" % (name, " / ".join(str(v) for v in pol),
+          "; the loop condition decided at the end of the step (hit %.3f per working step, dead %.3f of the rays that go on)"
+          % early_end_rates(c) if early_end else ""))
     for fuse, label in ((0, "shipped"), (1, "ENDED + refill falls into the march"), (2, "HIT falls into the march"), (3, "both")):
         p, ex, ln = shipped_pool(c, random.Random(1), fuse=fuse, t_hit=pol[0], t_end=pol[1], swap_min=pol[2], refill_min=pol[3],
-                                 keep=pol[4], max_iters=pol[5])
+                                 keep=pol[4], max_iters=pol[5], early_end=early_end)
         base = base or (p, ex["march"])
         print("fuse %d  %-36s passes %5.2f (%+5.1f%%)  march steps %5.2f (%+5.1f%%) at %4.1f lanes  hit %4.2f at %4.1f  ended %4.2f at %4.1f  exchanges %4.2f" % (
             fuse, label, p, 100 * (p / base[0] - 1), ex["march"], 100 * (ex["march"] / base[1] - 1), ln["march"], ex["hit"], ln["hit"],
@@ -368,7 +392,8 @@ def passes_table(name):
 
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "passes":
-        passes_table(sys.argv[2] if len(sys.argv) > 2 else "c3")
+        args = [a for a in sys.argv[2:] if a != "--early-end"]
+        passes_table(args[0] if args else "c3", early_end="--early-end" in sys.argv[2:])
         sys.exit(0)
     name = sys.argv[1] if len(sys.argv) > 1 else "c3"
     c = CFG[name]
