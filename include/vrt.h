@@ -596,6 +596,76 @@ int vrt_hit_owners(const vrt_scene* scene, const vrt_hit* d_hits, int64_t n_hits
                    const vrt_object* d_objects, int32_t n_objects, const uint8_t* d_models, const uint8_t* d_remap,
                    vrt_owner* d_owners, uint64_t* d_stats, void* stream);
 
+/* ---- surfaces of hit records ---------------------------------------------------------------------------
+ * HOW THE SURFACE LIES at a hit: the ray's velocity after the reference's reflection, the position one step on, what the
+ * three neighbour lookups of that reflection asked and found, and a geometric normal -- what mirror, portal and
+ * deferred-reflection passes that start at hit records need, and the normal image a G-buffer lacks.  The records say where
+ * a ray met a voxel (vrt_hit) and whose voxel it is (vrt_owner); the reflection also depends on the chunk the ray stood in,
+ * on chunk_get for a neighbour in another chunk and on that chunk's own LOD snap (init.py:92-111), which only the device
+ * scene can answer.  One 64-byte record per hit record. */
+typedef struct vrt_surface {   /* 64 bytes, 64-byte aligned array */
+    double  vel[3];        /* the ray's velocity after the hit: normalised, reflected axes scaled (below) */
+    double  next[3];       /* pos + vel * resolution: where the renderer's ray stands one step after the hit */
+    int8_t  normal[3];     /* geometric normal: one component -1 or +1, or all 0 (enclosed) */
+    int8_t  status;        /* 0 a surface; -1 the record is no hit (material <= 0); -2 orphan; -3 invalid input */
+    uint8_t neighbour[3];  /* material id the reflection test found per axis, 0 = none (or not asked: ior == 0) */
+    uint8_t resolution;    /* Frame.resolution of the chunk the ray stood in */
+    uint8_t reflect;       /* bit a: init.py:106-111 reflects axis a */
+    uint8_t side;          /* bit a: the neighbour asked on axis a lies at +1 (clear: -1) */
+    uint8_t fetched;       /* bit a: that neighbour was outside the current chunk (chunk_get, init.py:100-102) */
+    uint8_t open;          /* bit a: the incoming-side neighbour of the normal rule is empty */
+    uint8_t pad[4];
+} vrt_surface;
+enum { VRT_SURFACE_NONE = -1, VRT_SURFACE_ORPHAN = -2, VRT_SURFACE_INVALID = -3 };   /* vrt_surface.status */
+/* The words vrt_hit_surfaces writes into d_stats (every other word 0). */
+enum { VRT_S_SURFACE_EXAMINED = 8,    /* records with material > 0 */
+       VRT_S_SURFACE_RESOLVED = 4,    /* ... of them resolved (status 0) */
+       VRT_S_SURFACE_ORPHANS = 9,     /* ... of them that no chunk of the scene accounts for: the hits came from another scene */
+       VRT_S_SURFACE_AMBIGUOUS = 10,  /* records that TWO chunks explain differently; the first was taken (below) */
+       VRT_S_SURFACE_INVALID = 11,    /* ... of the examined that the device refused (examined = resolved + orphans + invalid) */
+       VRT_S_SURFACE_ENCLOSED = 12    /* resolved records with no open incoming side: normal (0, 0, 0) */ };
+
+/* d_surfaces[k] describes d_hits[k], reached by d_rays[k] (DEVICE arrays of n records: d_hits 8-byte, d_rays and d_surfaces
+ * 64-byte aligned).  Only `vel` of a ray record is read: the rays are what vrt_cast_rays was given, or what vrt_pixel_rays
+ * writes for the frame of a vrt_first_hit (for row 0 of vrt_path_rays likewise; the incoming velocities of a row's later
+ * hits are not recorded, so those are not offered).  Every field but `status` of a record with status < 0 is 0, and every
+ * byte of d_surfaces is defined after the call.
+ *   scene     the scene the hits were produced against: its camera table with the LOD bytes, as vrt_hit_owners takes it;
+ *             d_materials is read for `ior` only.
+ *   d_stats   [VRT_NSTATS] uint64, zeroed by the callee: the VRT_S_SURFACE_* words.
+ * Which chunk the ray stood in: vrt_hit_owners's rule.  The candidates are the chunk containing `cell` and, for every axis on
+ * which pos is a whole multiple of chunk_size, the chunk one below, in the order 000, 100, 010, 110, 001, 101, 011, 111; the
+ * first that is listed, contains (cell // r) * r and holds `material` there is the CURRENT chunk: cmin its origin,
+ * cmax = cmin + chunk_size (inclusive), r its resolution.  If none counts the record is an orphan (-2).  If a later candidate
+ * counts too and gives another vel, reflect or neighbour, the first is taken and the record is counted in
+ * VRT_S_SURFACE_AMBIGUOUS: "two chunks explain this record; the first was taken".
+ * The reflection (init.py:84, 92-111), in binary64 without contraction, in this order:  v = ray.vel;  ref = max |v[a]|, and
+ * v[a] /= ref if ref is neither 0 nor 1 (lib.py:310-314).  With ior of the hit's material: ior == 0 asks nothing
+ * (reflect = side = fetched = 0, neighbour 0).  Otherwise direction = (ior - 0.5) * 2 and, per axis a:  p = pos with
+ * p[a] = pos[a] + 1 if v[a] < direction, else pos[a] - 1;  the neighbour is read from the current chunk if cmin <= p <= cmax
+ * on all three axes, otherwise (fetched bit a) from the chunk the table lists for p snapped to chunk_size, and is absent if
+ * none is listed;  in either chunk it is read at (floor(p) // r') * r' with that chunk's own r', and is empty if that voxel
+ * lies outside the chunk;  axis a is reflected unless a neighbour was found and its material's ior equals the hit's:
+ * vel[a] = v[a] - v[a] * ior * 2.  Then next[a] = pos[a] + vel[a] * (double)r (init.py:114-116).
+ * For a material of roughness 0 this is, bit for bit, the renderer's ray one step after the hit (vrt_shade_rays's end state
+ * for a life that ends there).  For a ROUGH material lib.material jitters the velocity with three draws before the
+ * normalisation; vel and next are then the answer for the UNJITTERED velocity.
+ * The normal is this library's own definition, not the reference's (which has no normal: its reflection asks a side that
+ * depends on ior).  f = cell; for every axis with v[a] != 0 the cell q = f - sgn(v[a]) * e_a is OPEN if the chunk containing
+ * q is not listed, or its voxel at (q // r') * r' lies outside it, or is 0.  The normal is -sgn(v[a]) on the open axis with
+ * the largest |v[a]| (ties: the lowest axis), 0 on the other two; if no axis is open the hit is ENCLOSED: normal (0, 0, 0),
+ * counted in VRT_S_SURFACE_ENCLOSED.
+ * The records are device data and the call does not synchronise, so each record is validated on the device.  A record with
+ * material > 0 is INVALID -- status -3, counted, nothing further read for it -- when a pos or vel component is not finite,
+ * when |pos[a]| >= 2^28, when cell != floor(pos), or when material > n_materials.  Every table and voxel index is checked
+ * before it is used: no input makes the kernel read outside the scene's arrays.
+ * n = 0 only zeroes the statistics; n >= 2^32 is VRT_ERR_ARG, as is a NULL or misaligned array; more than 2^28 records are
+ * split into launches.  Every argument is checked before any HIP call; nothing is allocated or synchronised, so a call may
+ * be captured into a hipGraph.  (This entry point lives in a translation unit of its own: a launch failure returns
+ * VRT_ERR_HIP without updating vrt_last_hip_error().) */
+int vrt_hit_surfaces(const vrt_scene* scene, const vrt_hit* d_hits, const vrt_cast_ray* d_rays, int64_t n,
+                     vrt_surface* d_surfaces, uint64_t* d_stats, void* stream);
+
 /* Window.chunk_update's selection loop (init.py:447-452) on the device: which world chunks the camera renders this
  * frame and at which LOD.  The voxel blocks stay resident at full resolution; a chunk's LOD is only the resolution
  * byte of its table entry (a Frame of resolution r holds the voxels at coordinates divisible by r, which is what the

@@ -10,10 +10,10 @@ from . import data, lib
 from .data import Material, Frame, make_settings, load_settings, pixel_partition
 from .lib import vec3, quaternion, rgb, store, material, material_background
 from .scene import PackedScene
-from .camera import Camera, RenderResult, HitResult, CastResult, ShadeResult, PathResult, release_caches
+from .camera import Camera, RenderResult, HitResult, CastResult, ShadeResult, PathResult, SurfaceResult, release_caches
 from .canvas import Canvas
 from . import world
 from .world import OwnerResult
 
-__all__ = ["Camera", "RenderResult", "HitResult", "CastResult", "ShadeResult", "PathResult", "release_caches", "Canvas", "world", "OwnerResult", "Material", "Frame", "PackedScene", "data", "lib", "vec3", "quaternion", "rgb",
+__all__ = ["Camera", "RenderResult", "HitResult", "CastResult", "ShadeResult", "PathResult", "SurfaceResult", "release_caches", "Canvas", "world", "OwnerResult", "Material", "Frame", "PackedScene", "data", "lib", "vec3", "quaternion", "rgb",
            "store", "material", "material_background", "make_settings", "load_settings", "pixel_partition"]

@@ -17,7 +17,10 @@ DIAG_HIST = os.environ.get("VRT_DIAG", "0") == "2"
 # -DVRT_POOL_SLOTS=32); it is never built or rebuilt from here
 SO_OVERRIDE = os.environ.get("VRT_SO", "")
 SO_PATH = SO_OVERRIDE or os.path.join(HERE, ("_vrt_diaghist.so" if DIAG_HIST else "_vrt_diag.so") if DIAG else "_vrt.so")
-SOURCES = [os.path.join(HERE, "csrc", f) for f in ("vrt_kernels.hip", "vrt_math.h", "vrt_math_consts.h")]
+# the translation units of the one library (UNITS: vrt_surface.hip holds the surface pass, vrt_kernels.hip everything else) and
+# what they include: a change to any of them rebuilds it
+UNITS = [os.path.join(HERE, "csrc", f) for f in ("vrt_kernels.hip", "vrt_surface.hip")]
+SOURCES = UNITS + [os.path.join(HERE, "csrc", f) for f in ("vrt_math.h", "vrt_math_consts.h")]
 SOURCES.append(os.path.join(ROOT, "include", "vrt.h"))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared"] + \
@@ -38,6 +41,9 @@ S_RAYGEN_GROUPS = 15
 S_CAST_REJECTED = 9   # vrt_cast_rays only: rays the device refused (VRT_S_CAST_REJECTED)
 # vrt_hit_owners only (VRT_S_OWNER_*): records examined, resolved to an object, orphans, explained by two chunks
 S_OWNER_EXAMINED, S_OWNER_RESOLVED, S_OWNER_ORPHANS, S_OWNER_AMBIGUOUS = 8, 4, 9, 10
+# vrt_hit_surfaces only (VRT_S_SURFACE_*): records examined, resolved, orphans, explained differently by two chunks, refused
+# by the device, resolved with no open incoming side
+S_SURFACE_EXAMINED, S_SURFACE_RESOLVED, S_SURFACE_ORPHANS, S_SURFACE_AMBIGUOUS, S_SURFACE_INVALID, S_SURFACE_ENCLOSED = 8, 4, 9, 10, 11, 12
 
 
 def needs_build():
@@ -53,7 +59,7 @@ def build(force=False, verbose=False):
     """Compile python_raytracer_amd/_vrt.so for gfx950 (hipcc cross-compiles without a GPU)."""
     if not force and not needs_build():
         return SO_PATH
-    cmd = [HIPCC] + HIPCC_FLAGS + [SOURCES[0], "-o", SO_PATH]
+    cmd = [HIPCC] + HIPCC_FLAGS + UNITS + ["-o", SO_PATH]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -126,6 +132,20 @@ class VrtOwner(C.Structure):
 OWNER_FIELDS = [("object", "<i4"), ("resolution", "<i4"), ("voxel", "<i4", 3), ("local", "<i4", 3)]
 OWNER_BYTES = 32
 OWNER_NONE, OWNER_ORPHAN = -1, -2   # vrt_owner.object of a record that is no hit / that no object accounts for
+
+
+class VrtSurface(C.Structure):
+    """vrt_surface (include/vrt.h): how the surface lies at a hit record -- the velocity after the reflection, the position
+    one step on, the normal, what the neighbour lookups asked and found, 64 bytes."""
+    _fields_ = [("vel", C.c_double * 3), ("next", C.c_double * 3), ("normal", C.c_int8 * 3), ("status", C.c_int8),
+                ("neighbour", C.c_uint8 * 3), ("resolution", C.c_uint8), ("reflect", C.c_uint8), ("side", C.c_uint8),
+                ("fetched", C.c_uint8), ("open", C.c_uint8), ("pad", C.c_uint8 * 4)]
+
+
+SURFACE_FIELDS = [("vel", "<f8", 3), ("next", "<f8", 3), ("normal", "i1", 3), ("status", "i1"), ("neighbour", "u1", 3),
+                  ("resolution", "u1"), ("reflect", "u1"), ("side", "u1"), ("fetched", "u1"), ("open", "u1"), ("pad", "u1", 4)]
+SURFACE_BYTES = 64
+SURFACE_OK, SURFACE_NONE, SURFACE_ORPHAN, SURFACE_INVALID = 0, -1, -2, -3   # vrt_surface.status
 
 
 class VrtEdit(C.Structure):
@@ -236,6 +256,8 @@ def lib():
     L.vrt_voxelize.argtypes = [vp, i32, vp, vp, C.POINTER(i64), C.POINTER(i32), i32, vp, i64, vp, vp, vp]
     L.vrt_hit_owners.restype = C.c_int
     L.vrt_hit_owners.argtypes = [C.POINTER(VrtScene), vp, i64, vp, i32, vp, vp, vp, vp, vp]
+    L.vrt_hit_surfaces.restype = C.c_int
+    L.vrt_hit_surfaces.argtypes = [C.POINTER(VrtScene), vp, vp, i64, vp, vp, vp]
     L.vrt_edit_models.restype = C.c_int
     L.vrt_edit_models.argtypes = [vp, i64, vp, i32, vp, vp]
     L.vrt_stamp_model.restype = C.c_int
@@ -274,7 +296,7 @@ EXPORTS = ["vrt_abi_version", "vrt_status_string", "vrt_last_hip_error", "vrt_de
            "vrt_pow_memo_create", "vrt_occupancy_build", "vrt_canvas_blit", "vrt_world_tables_bytes", "vrt_world_tables_build",
            "vrt_trace_workspace_bytes", "vrt_trace_rays", "vrt_rng_draws",
            "vrt_synth_volume", "vrt_profile_begin", "vrt_profile_begin_kinds", "vrt_profile_end", "vrt_select_chunks", "vrt_voxelize",
-           "vrt_hit_owners", "vrt_edit_models", "vrt_stamp_model"]
+           "vrt_hit_owners", "vrt_hit_surfaces", "vrt_edit_models", "vrt_stamp_model"]
 
 
 PLAN_FIELDS = ("launches", "pool", "wt_on", "trav_words", "bm_window", "ct_cells", "n_materials", "dyn_bytes", "static_bytes")

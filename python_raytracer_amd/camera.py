@@ -14,7 +14,7 @@ from . import _native as nat
 from . import data as _data
 from .lib import vec3, quaternion, rgb, store, is_default_background
 from .scene import PackedScene
-from .results import RenderResult, HitResult, CastResult, ShadeResult, PathResult, _traversed_positions
+from .results import RenderResult, HitResult, CastResult, ShadeResult, PathResult, SurfaceResult, _traversed_positions
 
 
 def _xyz(v):
@@ -1116,6 +1116,57 @@ class Camera:
             nat.check(rc, "vrt_pixel_rays")
             used = rays[:, 6] == rays[:, 6]   # (an unused slot is NaN throughout)
         return rays, used
+
+    # ------------------------------------------------------------------ hit records: how the surface lies there
+    def surfaces(self, hits, rays, stream=None):
+        """How the surface lies at hit records (vrt_hit_surfaces): per record the ray's velocity after the reference's
+        reflection (init.py:84, 92-111), its position one step on, the neighbours that reflection asked and found, and a
+        geometric normal -- where a mirror, portal or deferred-reflection pass goes on from a hit, and the normal image of a
+        G-buffer.  For a material of roughness 0 velocity and position are bit for bit the renderer's ray one step after the
+        hit; for a rough one they are the answer for the unjittered velocity.
+        hits: a HitResult (first_hit), a CastResult (cast_rays), PathResult.hit(0), or a uint8 tensor of 48-byte vrt_hit
+        records on this camera's device.  rays: the rays that reached them -- what pixel_rays returned (the tensor, or the
+        (rays, used) pair) or what cast_rays was given: ONE [n, 8] float64 CUDA tensor of vrt_cast_ray records, or a tuple
+        (origins, velocities); only the velocities are read.
+        The records go against the scene this camera currently renders, with the LODs of its last chunk_update(), as
+        DeviceWorld.owners(hits, camera) resolves them.
+        Returns a SurfaceResult of device tensors; nothing is copied to the host and nothing synchronises (with tensors
+        already on the device the call can be captured into a graph)."""
+        torch = self._torch
+        dev = self._require_device()
+        records = getattr(hits, "records", hits)
+        if not isinstance(records, torch.Tensor) or records.dtype != torch.uint8:
+            raise ValueError("surfaces(): hits must be a HitResult, a CastResult or a uint8 tensor of vrt_hit records")
+        if records.device != dev:
+            raise ValueError("surfaces(): the hit records are on %s, the camera renders on %s" % (records.device, dev))
+        if records.numel() % nat.HIT_BYTES:
+            raise ValueError("surfaces(): %d bytes are no whole number of %d-byte vrt_hit records" % (records.numel(), nat.HIT_BYTES))
+        n = records.numel() // nat.HIT_BYTES
+        if n >= 1 << 32:
+            raise ValueError("surfaces: 2**32 records and more need several calls")
+        if isinstance(rays, tuple) and len(rays) == 2 and isinstance(rays[1], torch.Tensor) and rays[1].dtype == torch.bool:
+            rays = rays[0]   # (pixel_rays's (rays, used))
+        if isinstance(rays, tuple) and len(rays) != 2:
+            raise ValueError("surfaces(): rays must be one [n, 8] tensor of vrt_cast_ray records or (origins, velocities)")
+        n_rays = len(rays[0]) if isinstance(rays, tuple) else (int(rays.shape[0]) if hasattr(rays, "shape") and len(rays.shape) else -1)
+        if n_rays != n:   # (before anything is launched)
+            raise ValueError("surfaces(): %d hit records but %d rays" % (n, n_rays))
+        sc = self._ensure_scene()
+        with torch.cuda.device(dev), self._on_stream(stream):
+            origins, velocities = rays if isinstance(rays, tuple) else (rays, None)
+            rec = self._cast_records(origins, velocities, None, 0.0, "surfaces")
+            if not records.is_contiguous():   # (PathResult.hit(0) of rows longer than one record)
+                records = records.contiguous()
+            records = records.reshape(-1)
+            if records.data_ptr() % 8:
+                raise ValueError("surfaces(): the hit records must be 8-byte aligned")
+            csc = self._c_scene(sc)
+            out = torch.empty(max(n, 1) * nat.SURFACE_BYTES, dtype=torch.uint8, device=dev)
+            stats = torch.empty(nat.NSTATS, dtype=torch.int64, device=dev)   # (the library clears it)
+            rc = nat.lib().vrt_hit_surfaces(C.byref(csc), records.data_ptr() if n else None, rec.data_ptr() if n else None, n,
+                                            out.data_ptr(), stats.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            nat.check(rc, "vrt_hit_surfaces")
+        return SurfaceResult(out[: n * nat.SURFACE_BYTES], stats)
 
     def line_of_sight(self, a, b, stream=None):
         """torch.bool [n]: can point a[k] see point b[k]?  One cast per pair: vel = (b - a) / max|b - a| -- the reference's

@@ -225,3 +225,80 @@ class ShadeResult(_LazyStats):
         """Visited chunk positions inside the box the call was given, in the reference's order (the order-preserving union
         over the rays in array order); [] without a box."""
         return _traversed_positions(self.traversed_keys, self.trav_origin, self.trav_dims, chunk_size)
+
+
+class SurfaceResult(_LazyStats):
+    """Device-side records of Camera.surfaces(): views of one buffer of 64-byte vrt_surface records (include/vrt.h), record k
+    for hit record k -- how the surface lies there.
+    `stats`: numpy int64[16], copied from the device on first use (a synchronisation): word 8 = records with a material
+    examined, word 4 = resolved (status 0), word 9 = orphans (no chunk of the scene accounts for them), word 10 = records two
+    chunks explain differently, of which the first was taken, word 11 = records the device refused, word 12 = resolved records
+    with no open incoming side (normal 0)."""
+
+    def __init__(self, records, stats_dev):
+        import torch
+        n = records.numel() // nat.SURFACE_BYTES
+        f64 = records.view(torch.float64).view(n, nat.SURFACE_BYTES // 8)
+        i8 = records.view(torch.int8).view(n, nat.SURFACE_BYTES)
+        u8 = records.view(n, nat.SURFACE_BYTES)
+        self.records = records           # uint8 [n * 64]
+        self.vel = f64[:, 0:3]           # float64 [n, 3]: the velocity after the hit (of the unjittered ray: include/vrt.h)
+        self.next = f64[:, 3:6]          # float64 [n, 3]: pos + vel * resolution, the ray's position one step on
+        self.normal = i8[:, 48:51]       # int8 [n, 3]: one component -1 or +1; all 0: enclosed, or no surface
+        self.status = i8[:, 51]          # int8 [n]: 0 a surface, -1 no hit, -2 orphan, -3 invalid input
+        self.neighbour = u8[:, 52:55]    # uint8 [n, 3]: the material the reflection test found per axis (0: none)
+        self.resolution = u8[:, 55]      # uint8 [n]: resolution of the chunk the ray stood in
+        self.reflect = u8[:, 56]         # uint8 [n]: bit a: axis a is reflected
+        self.side = u8[:, 57]            # uint8 [n]: bit a: the neighbour asked on axis a lies at +1
+        self.fetched = u8[:, 58]         # uint8 [n]: bit a: that neighbour came through chunk_get
+        self.open = u8[:, 59]            # uint8 [n]: bit a: the incoming-side neighbour of the normal rule is empty
+        self._stats_dev = stats_dev
+
+    def numpy(self):
+        """The records as a numpy structured array (fields of vrt_surface)."""
+        return np.ascontiguousarray(self.records.cpu().numpy()).view(np.dtype(nat.SURFACE_FIELDS)).reshape(-1)
+
+    def surface_mask(self):
+        """torch.bool [n]: the record describes a surface (status 0)."""
+        return self.status == nat.SURFACE_OK
+
+    def reflect_mask(self):
+        """torch.bool [n, 3]: axis a of record k is reflected (always false where there is no surface)."""
+        import torch
+        bits = torch.tensor([1, 2, 4], dtype=torch.uint8, device=self.records.device)
+        return (self.reflect[:, None] & bits[None, :]) != 0
+
+    def normal_image(self, hit_result):
+        """[height, width, 3] int8 normal image of the HitResult these surfaces were made from: the normal sample 0 of every
+        pixel sees; 0 where it sees no surface and at pixels that are not listed."""
+        import torch
+        if hit_result.records.numel() // nat.HIT_BYTES != self.status.numel():
+            raise ValueError("normal_image(): these surfaces were not made from that HitResult")
+        return torch.stack([hit_result._scatter(self.normal[:, a], 0, torch.int8) for a in range(3)], dim=-1)
+
+    def rays(self, lives):
+        """The continuation rays as explicit rays: a [n, 8] float64 CUDA tensor of vrt_cast_ray records with origin = next,
+        vel = vel and life = lives (a number, or [n]), which cast_rays, shade_rays and path_rays take as it is.  Records with
+        status < 0 are eight NaNs, which every explicit-ray call rejects.  The doubles are copied, never computed with.
+        A continuation starts with no current chunk: a ray that lands exactly on its old chunk's inclusive upper face re-snaps
+        into the chunk above there, where the renderer's ray would have stayed in the old one."""
+        import torch
+        n = self.status.numel()
+        dev = self.records.device
+        rec = torch.empty((max(n, 1), 8), dtype=torch.float64, device=dev)[:n]
+        rec[:, 0:3] = self.next
+        rec[:, 3:6] = self.vel
+        if isinstance(lives, torch.Tensor):
+            if lives.numel() != n:
+                raise ValueError("rays(): %d lives for %d records" % (lives.numel(), n))
+            rec[:, 6] = lives.to(device=dev, dtype=torch.float64).reshape(n)
+        elif np.ndim(lives) == 0:
+            rec[:, 6] = float(lives)
+        else:
+            host = np.ascontiguousarray(lives, np.float64).reshape(-1)
+            if host.size != n:
+                raise ValueError("rays(): %d lives for %d records" % (host.size, n))
+            rec[:, 6] = torch.from_numpy(host).to(dev)
+        rec[:, 7] = 0.0
+        # (a select, which neither computes with a double nor synchronises as an assignment through a mask would)
+        return torch.where((self.status < 0)[:, None], torch.full_like(rec, float("nan")), rec)
