@@ -666,6 +666,86 @@ enum { VRT_S_SURFACE_EXAMINED = 8,    /* records with material > 0 */
 int vrt_hit_surfaces(const vrt_scene* scene, const vrt_hit* d_hits, const vrt_cast_ray* d_rays, int64_t n,
                      vrt_surface* d_surfaces, uint64_t* d_stats, void* stream);
 
+/* ---- object physics ------------------------------------------------------------------------------------
+ * One physics tick of the reference, `for obj in objects: obj.update(cam_pos)` (init.py:469-470; Object.update_physics,
+ * data.py:495-560), on the resident models: voxel-against-voxel collision between objects read through their quarter
+ * turns, velocity transfer between physical objects, friction, elasticity, gravity and the velocity bounds.
+ * One body per object of the world, in the world's order -- the physics order.  192 bytes, 8-byte aligned.  The embedded
+ * vrt_object is what vrt_voxelize would be given for the object (model, shape, turns, remap); its mins and maxs are the
+ * body's box and the kernel keeps them current: after the call they are ceil(pos) - half and floor(pos) + half of a body
+ * that moved.  Unlike vrt_voxelize the physics reads the box INCLUSIVE of maxs (data.py:463-464, 532-534). */
+typedef struct vrt_body {
+    double  pos[3];          /* in, out: the centre */
+    double  vel[3];          /* in, out */
+    double  weight;          /* in: Object.weight */
+    vrt_object object;       /* in; mins and maxs in, out */
+    int32_t half[3];         /* in: trunc(sprite size / 2), Object.size */
+    int32_t visible_before;  /* in: Object.visible as the last tick left it */
+    int32_t visible_now;     /* in: what Object.update makes of it this tick, from the position at the start of the tick */
+    int32_t awake;           /* in: that distance <= dist_move */
+    int32_t physics;         /* in: Object.physics */
+    int32_t has_sprite;      /* in: 0: no model; such a body neither moves nor is met */
+    int32_t steps;           /* out: moves tried (iterations of data.py:500) */
+    int32_t blocked_steps;   /* out: ... of them blocked */
+    int32_t contacts;        /* out: pairs of solid voxels that met, over all steps */
+    int32_t transfers;       /* out: velocity transfers to physical neighbours */
+    int32_t moved;           /* out: 1 if the position changed (Object.move set redraw) */
+    int32_t status;          /* out: 0 stepped; -1 skipped (not visible, asleep, not physical); -3 refused */
+    int64_t rim;             /* in: offset in d_models of the plane [size.y][size.z] of model bytes at x = size.x, -1: empty (below) */
+    int32_t pad[2];
+} vrt_body;
+enum { VRT_BODY_SKIPPED = -1, VRT_BODY_REFUSED = -3 };   /* vrt_body.status */
+typedef struct vrt_physics_params {
+    double gravity, friction, friction_air, min_velocity, max_velocity;   /* settings of the [PHYSICS] section */
+} vrt_physics_params;
+/* The words vrt_physics_tick writes into d_stats (every other word 0). */
+enum { VRT_S_PHYSICS_BODIES = 8,      /* bodies stepped (status 0) */
+       VRT_S_PHYSICS_REFUSED = 9,     /* bodies the device refused (status -3) */
+       VRT_S_PHYSICS_STEPS = 10,      /* steps of all bodies */
+       VRT_S_PHYSICS_BLOCKED = 11,    /* ... of them blocked */
+       VRT_S_PHYSICS_CONTACTS = 12,
+       VRT_S_PHYSICS_TRANSFERS = 13,
+       VRT_S_PHYSICS_CAPPED = 14      /* bodies whose step loop was ended by the iteration cap (below) */ };
+#define VRT_PHYSICS_MAX_VEL 1024       /* |vel|_inf above this: refused */
+#define VRT_PHYSICS_MAX_HALF 1024      /* half or a box extent beyond 2 * this + 1: refused */
+#define VRT_PHYSICS_STEP_CAP (3 * (VRT_PHYSICS_MAX_VEL + 2))
+
+/* The tick is a sequential chain by the reference's semantics: body k meets the positions bodies 0..k-1 have just taken and
+ * the velocity they have just handed it, and the steps of one body follow each other.  So the call is ONE launch of ONE
+ * workgroup of 1024 threads that walks the bodies in array order and synchronises with workgroup barriers only; the width
+ * goes to the work inside a step -- the slab of world voxels the body would enter, times the bodies whose boxes meet it.
+ * Another body j is met by body k if it is visible -- visible_now for j < k, visible_before for j > k: Object.update refreshes
+ * an object's flag immediately before its own physics -- has a sprite, was not refused, and its inclusive box meets the slab.
+ * A physical one first takes vel_apply * max(0, min(1, max|vel_apply| * weight_k - weight_j)) (data.py:523-527), contact or
+ * not.  Then every slab voxel asks j's model for its byte at `voxel - mins_j` through j's turns (vrt_voxelize's question;
+ * positions outside the model hold nothing -- except the plane at model x = size.x, `rim`: the reference's import mirrors x as
+ * size.x - x (data.py:287), so a file's x = 0 column lands there, outside the model vrt_voxelize reads, and the inclusive box
+ * test above reaches it; the default mod's cubes rest on such voxels); if that material is solid, body k's own model is asked at `voxel - mins_k -
+ * vel_dir` through k's turns; two solid voxels are a contact: the step is blocked and
+ * friction += f_j * f_k * params.friction, elasticity += e_j * e_k * params.friction, evaluated left to right in binary64
+ * without contraction and ADDED IN THE REFERENCE'S ORDER, bodies -> x -> y -> z (contacts are compacted in that order and one
+ * lane adds them: a tree reduction gives other low bits).
+ *   d_matphys   [n_materials + 1][4] doubles by world material id: solidity, friction, elasticity, 0 (row 0 unused);
+ *               d_remap[object.remap + model byte] is the id.  A material is SOLID iff solidity >= 1: `solidity >
+ *               random.random()` is then always true, and for solidity <= 0 always false.  Fractional solidities need the
+ *               draws in the reference's order and are the host path's (world.tick); the device treats them as not solid.
+ *   d_stats     [VRT_NSTATS] uint64, zeroed by the callee: the VRT_S_PHYSICS_* words.
+ * The bodies are device data, so each is validated on the device.  A body is REFUSED -- status -3, counted, neither moved nor
+ * met, its velocity untouched -- when a pos or vel component or the weight is not finite, |pos[a]| >= 2^28, |vel[a]| > VRT_PHYSICS_MAX_VEL,
+ * half[a] < 0 or > VRT_PHYSICS_MAX_HALF, its box is not 0 <= maxs - mins <= 2 * VRT_PHYSICS_MAX_HALF + 1 inside +-2^29, or
+ * (with has_sprite) its model shape is not 0 <= size[a] <= 32768, its model leaves [0, models_bytes), as its rim plane if rim is not -1, or its remap
+ * offset leaves [0, remap_bytes).  A remap index or material id out of range reads as "no voxel".  No input makes the kernel read
+ * outside d_models, d_remap or d_matphys.  The step loop of a body ends after VRT_PHYSICS_STEP_CAP iterations at the latest,
+ * which a valid body cannot reach (each step takes 1 off the largest component or clears it); a hit is counted in
+ * VRT_S_PHYSICS_CAPPED.  The kernel terminates on any input.
+ * n_bodies = 0 only zeroes the statistics.  VRT_ERR_ARG, before any HIP call: NULL d_stats or params, n_bodies < 0 or
+ * > 2^20, NULL or misaligned (8 bytes) d_bodies or d_matphys with n_bodies > 0, negative sizes, NULL d_models with
+ * models_bytes > 0 or d_remap with remap_bytes > 0, n_materials > 255, params that are not finite.  Nothing is allocated or
+ * synchronised.  (A translation unit of its own: a launch failure returns VRT_ERR_HIP without updating vrt_last_hip_error().) */
+int vrt_physics_tick(vrt_body* d_bodies, int32_t n_bodies, const uint8_t* d_models, int64_t models_bytes,
+                     const uint8_t* d_remap, int32_t remap_bytes, const double* d_matphys, int32_t n_materials,
+                     const vrt_physics_params* params, uint64_t* d_stats, void* stream);
+
 /* Window.chunk_update's selection loop (init.py:447-452) on the device: which world chunks the camera renders this
  * frame and at which LOD.  The voxel blocks stay resident at full resolution; a chunk's LOD is only the resolution
  * byte of its table entry (a Frame of resolution r holds the voxels at coordinates divisible by r, which is what the

@@ -14,6 +14,7 @@ from .camera import Camera, RenderResult, HitResult, CastResult, ShadeResult, Pa
 from .canvas import Canvas
 from . import world
 from .world import OwnerResult
+from .results import PhysicsResult
 
-__all__ = ["Camera", "RenderResult", "HitResult", "CastResult", "ShadeResult", "PathResult", "SurfaceResult", "release_caches", "Canvas", "world", "OwnerResult", "Material", "Frame", "PackedScene", "data", "lib", "vec3", "quaternion", "rgb",
+__all__ = ["Camera", "RenderResult", "HitResult", "CastResult", "ShadeResult", "PathResult", "SurfaceResult", "release_caches", "Canvas", "world", "OwnerResult", "PhysicsResult", "Material", "Frame", "PackedScene", "data", "lib", "vec3", "quaternion", "rgb",
            "store", "material", "material_background", "make_settings", "load_settings", "pixel_partition"]

@@ -20,7 +20,9 @@ SO_PATH = SO_OVERRIDE or os.path.join(HERE, ("_vrt_diaghist.so" if DIAG_HIST els
 # the translation units of the one library (UNITS: vrt_surface.hip holds the surface pass, vrt_kernels.hip everything else) and
 # what they include: a change to any of them rebuilds it
 UNITS = [os.path.join(HERE, "csrc", f) for f in ("vrt_kernels.hip", "vrt_surface.hip")]
-SOURCES = UNITS + [os.path.join(HERE, "csrc", f) for f in ("vrt_math.h", "vrt_math_consts.h")]
+# the object physics (vrt_physics_tick) is a third unit of the same library, listed on its own
+PHYSICS_UNITS = [os.path.join(HERE, "csrc", "vrt_physics.hip")]
+SOURCES = UNITS + PHYSICS_UNITS + [os.path.join(HERE, "csrc", f) for f in ("vrt_math.h", "vrt_math_consts.h")]
 SOURCES.append(os.path.join(ROOT, "include", "vrt.h"))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared"] + \
@@ -59,7 +61,7 @@ def build(force=False, verbose=False):
     """Compile python_raytracer_amd/_vrt.so for gfx950 (hipcc cross-compiles without a GPU)."""
     if not force and not needs_build():
         return SO_PATH
-    cmd = [HIPCC] + HIPCC_FLAGS + UNITS + ["-o", SO_PATH]
+    cmd = [HIPCC] + HIPCC_FLAGS + UNITS + PHYSICS_UNITS + ["-o", SO_PATH]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -158,6 +160,37 @@ EDIT_FIELDS = [("model", "<i8"), ("size", "<i4", 3), ("lo", "<i4", 3), ("hi", "<
                ("pad", "<i4", 3)]
 EDIT_BYTES = 64
 S_EDIT_INVALID = 9   # vrt_edit_models only (VRT_S_EDIT_INVALID): records the device refused
+
+
+class VrtBody(C.Structure):
+    """vrt_body (include/vrt.h): one object of a physics tick, 192 bytes; `object` is its vrt_object."""
+    _fields_ = [("pos", C.c_double * 3), ("vel", C.c_double * 3), ("weight", C.c_double), ("object", VrtObject),
+                ("half", C.c_int32 * 3), ("visible_before", C.c_int32), ("visible_now", C.c_int32), ("awake", C.c_int32),
+                ("physics", C.c_int32), ("has_sprite", C.c_int32), ("steps", C.c_int32), ("blocked_steps", C.c_int32),
+                ("contacts", C.c_int32), ("transfers", C.c_int32), ("moved", C.c_int32), ("status", C.c_int32),
+                ("rim", C.c_int64), ("pad", C.c_int32 * 2)]
+
+
+OBJECT_FIELDS = [("mins", "<i4", 3), ("maxs", "<i4", 3), ("size", "<i4", 3), ("turns", "<i4", 3), ("model", "<i8"), ("remap", "<i4"),
+                 ("pad", "<i4")]
+BODY_FIELDS = [("pos", "<f8", 3), ("vel", "<f8", 3), ("weight", "<f8"), ("object", OBJECT_FIELDS), ("half", "<i4", 3),
+               ("visible_before", "<i4"), ("visible_now", "<i4"), ("awake", "<i4"), ("physics", "<i4"), ("has_sprite", "<i4"),
+               ("steps", "<i4"), ("blocked_steps", "<i4"), ("contacts", "<i4"), ("transfers", "<i4"), ("moved", "<i4"),
+               ("status", "<i4"), ("rim", "<i8"), ("pad", "<i4", 2)]
+BODY_BYTES = 192
+BODY_OK, BODY_SKIPPED, BODY_REFUSED = 0, -1, -3   # vrt_body.status
+
+
+class VrtPhysicsParams(C.Structure):
+    """vrt_physics_params (include/vrt.h): the [PHYSICS] settings a tick reads."""
+    _fields_ = [("gravity", C.c_double), ("friction", C.c_double), ("friction_air", C.c_double), ("min_velocity", C.c_double),
+                ("max_velocity", C.c_double)]
+
+
+# vrt_physics_tick only (VRT_S_PHYSICS_*): bodies stepped, refused, steps, blocked steps, contacts, transfers, iteration-cap hits
+S_PHYSICS_BODIES, S_PHYSICS_REFUSED, S_PHYSICS_STEPS, S_PHYSICS_BLOCKED = 8, 9, 10, 11
+S_PHYSICS_CONTACTS, S_PHYSICS_TRANSFERS, S_PHYSICS_CAPPED = 12, 13, 14
+PHYSICS_MAX_VEL, PHYSICS_MAX_HALF, PHYSICS_STEP_CAP = 1024, 1024, 3 * (1024 + 2)
 
 _lib = None
 
@@ -262,6 +295,8 @@ def lib():
     L.vrt_edit_models.argtypes = [vp, i64, vp, i32, vp, vp]
     L.vrt_stamp_model.restype = C.c_int
     L.vrt_stamp_model.argtypes = [vp, i64, i64, i64, C.POINTER(i32), vp, i32, vp]
+    L.vrt_physics_tick.restype = C.c_int
+    L.vrt_physics_tick.argtypes = [vp, i32, vp, i64, vp, i32, vp, i32, C.POINTER(VrtPhysicsParams), vp, vp]
     L.vrt_canvas_blit.restype = C.c_int
     L.vrt_canvas_blit.argtypes = [vp, vp, i32, i32, vp, i64, vp]
     L.vrt_profile_begin.restype = C.c_int
@@ -296,7 +331,7 @@ EXPORTS = ["vrt_abi_version", "vrt_status_string", "vrt_last_hip_error", "vrt_de
            "vrt_pow_memo_create", "vrt_occupancy_build", "vrt_canvas_blit", "vrt_world_tables_bytes", "vrt_world_tables_build",
            "vrt_trace_workspace_bytes", "vrt_trace_rays", "vrt_rng_draws",
            "vrt_synth_volume", "vrt_profile_begin", "vrt_profile_begin_kinds", "vrt_profile_end", "vrt_select_chunks", "vrt_voxelize",
-           "vrt_hit_owners", "vrt_hit_surfaces", "vrt_edit_models", "vrt_stamp_model"]
+           "vrt_hit_owners", "vrt_hit_surfaces", "vrt_edit_models", "vrt_stamp_model", "vrt_physics_tick"]
 
 
 PLAN_FIELDS = ("launches", "pool", "wt_on", "trav_words", "bm_window", "ct_cells", "n_materials", "dyn_bytes", "static_bytes")

@@ -1,8 +1,9 @@
 """Host-side scene inputs of the trace path: render settings, the pixel partition, Material and Frame.
 
 Mirrors the parts of the reference's `data` module that Camera.tile / Camera.trace read
-(reference data.py:15-77 settings + pixels, 85-93 Material, 96-145 Frame lookup).  Physics, sprites,
-objects and the mod loader are out of scope.
+(reference data.py:15-77 settings + pixels, 85-93 Material, 96-145 Frame lookup), and the [PHYSICS] settings
+world.tick / DeviceWorld.tick read.  Sprites and objects live in world.py; the mod loader is out of scope
+(SURVEY.md section 8).
 """
 import configparser
 
@@ -16,6 +17,10 @@ _FLOAT_KEYS = dict(shutter=0.0, falloff=0.0, fov=90.0, dof=0.0, max_light=0.0, m
                    lod_samples=0.0, lod_random=0.0, lod_edge=0.0)
 _BOOL_KEYS = dict(static=False, culling=False, sync=False)
 _SECTION = dict(width="WINDOW", height="WINDOW")
+# keys of the [PHYSICS] section Object.update_physics / Object.update read (reference data.py:52-62), same idiom; nothing of the
+# trace path reads them
+_PHYSICS_FLOAT_KEYS = dict(gravity=0, friction=0, friction_air=0, min_velocity=0, max_velocity=0)
+_PHYSICS_INT_KEYS = dict(dist_move=0)
 
 
 class PixelList:
@@ -61,7 +66,9 @@ def make_settings(**overrides):
     """Settings store with the default mod's [RENDER] values (reference mods/default/config.cfg:1-34)."""
     s = store(width=64, height=48, samples=1, static=True, culling=True, sync=False, shutter=0.25, falloff=0.25,
               chunk_size=16, chunk_lod=2, fov=90.0, dof=0.5, dist_min=0, dist_max=192, max_light=1.0,
-              max_bounces=2.0, lod_bounces=0.5, lod_samples=0.5, lod_random=0.25, lod_edge=0.25, threads=1)
+              max_bounces=2.0, lod_bounces=0.5, lod_samples=0.5, lod_random=0.25, lod_edge=0.25, threads=1,
+              # [PHYSICS] (mods/default/config.cfg:36-47)
+              gravity=1.0, friction=1.0, friction_air=0.1, min_velocity=0.01, max_velocity=10.0, dist_move=64)
     for k, v in overrides.items():
         setattr(s, k, v)
     return finalize_settings(s)
@@ -81,6 +88,10 @@ def load_settings(path, threads=None):
         setattr(s, k, cfg.getfloat("RENDER", k) or d)
     for k, d in _BOOL_KEYS.items():
         setattr(s, k, cfg.getboolean("RENDER", k) or d)
+    for k, d in _PHYSICS_FLOAT_KEYS.items():   # (a config without the section, as older ones of this project's, gets the defaults)
+        setattr(s, k, cfg.getfloat("PHYSICS", k, fallback=0) or d)
+    for k, d in _PHYSICS_INT_KEYS.items():
+        setattr(s, k, cfg.getint("PHYSICS", k, fallback=0) or d)
     if threads is not None:
         s.threads = threads
     if not s.threads:

@@ -57,6 +57,48 @@ class vec3:
             return (self.x, self.y, self.z) == (o.x, o.y, o.z)
         return self.x == o and self.y == o and self.z == o
 
+    def __le__(self, o):
+        """Every component at once, as the reference compares boxes (lib.py:228-244)."""
+        if isinstance(o, vec3):
+            return self.x <= o.x and self.y <= o.y and self.z <= o.z
+        return self.x <= o and self.y <= o and self.z <= o
+
+    def __ge__(self, o):
+        if isinstance(o, vec3):
+            return self.x >= o.x and self.y >= o.y and self.z >= o.z
+        return self.x >= o and self.y >= o and self.z >= o
+
+    def __abs__(self):
+        return vec3(abs(self.x), abs(self.y), abs(self.z))
+
+    def __trunc__(self):
+        return vec3(math.trunc(self.x), math.trunc(self.y), math.trunc(self.z))
+
+    def __floor__(self):
+        return vec3(math.floor(self.x), math.floor(self.y), math.floor(self.z))
+
+    def __ceil__(self):
+        return vec3(math.ceil(self.x), math.ceil(self.y), math.ceil(self.z))
+
+    def mins(self):
+        return min(self.x, self.y, self.z)
+
+    def maxs(self):
+        return max(self.x, self.y, self.z)
+
+    def min(self, o):
+        return self._map(o, min)
+
+    def max(self, o):
+        return self._map(o, max)
+
+    def normalize(self):
+        """Divide by the largest magnitude: a Chebyshev normalisation (reference lib.py:310-314)."""
+        ref = abs(self).maxs()
+        if ref and ref != 1:
+            return vec3(self.x, self.y, self.z) / ref
+        return self
+
     def __hash__(self):
         return hash((self.x, self.y, self.z))
 

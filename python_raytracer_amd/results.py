@@ -302,3 +302,20 @@ class SurfaceResult(_LazyStats):
         rec[:, 7] = 0.0
         # (a select, which neither computes with a double nor synchronises as an assignment through a mask would)
         return torch.where((self.status < 0)[:, None], torch.full_like(rec, float("nan")), rec)
+
+
+class PhysicsResult(_LazyStats):
+    """What DeviceWorld.tick() did.  `moved`: the Objects whose position changed, in physics order.  `records`: the body
+    records as read back, a numpy structured array of vrt_body (include/vrt.h), one per object.  `counters`: its `out` fields
+    alone (steps, blocked_steps, contacts, transfers, moved, status: 0 stepped, -1 skipped, -3 refused) -- the array
+    world.tick() returns for the same tick.  `kernel_ms`: the kernel's time if it was asked for, else None.
+    `stats`: numpy int64[16], copied from the device on first use: word 8 = bodies stepped, 9 = refused, 10 = steps, 11 = blocked
+    steps, 12 = contacts, 13 = transfers, 14 = bodies the iteration cap ended."""
+
+    def __init__(self, records, moved, stats_dev, kernel_ms=None):
+        from .world import PHYSICS_COUNTER_FIELDS
+        self.records, self.moved, self.kernel_ms = records, moved, kernel_ms
+        self.counters = np.zeros(len(records), np.dtype(PHYSICS_COUNTER_FIELDS))
+        for name, *_ in PHYSICS_COUNTER_FIELDS:
+            self.counters[name] = records[name]
+        self._stats_dev = stats_dev
