@@ -24,6 +24,8 @@ the box test of data.py:463-464 reaches: the default mod's cubes rest on it.  Th
 (vrt_body.rim) and nothing else outside the size.  So each device scene runs a second time with lookups restricted to what the
 device holds; that run, too, must equal the reference's in every field, counts included.  `outside` in `reached` says how many
 voxels the reference's lookups found outside the sprites' sizes.
+The scene `crowd` has more bodies than the device walks at a time; its file is written only if the run also shows what that scene
+is for (crowd_reach).  A file whose arrays come out as they are on disk is not written again.
 
 Usage:  python tests/golden/make_physics.py
 """
@@ -157,6 +159,60 @@ REACH = dict(blocked_steps=30, transfers_inside=5, transfers_one=1, body_ticks_3
              steps_over_256_contacts=1, order_dependent_sums=1)
 
 
+TILE = 1024     # the bodies the device walks at a time (vrt_physics.hip, VRT_PHYS_BLOCK)
+CROWD_REACH = ("contacts_both_sides_one_step", "transfers_both_sides_one_step", "movers_from_1024", "visible_before_met", "visible_now_met")
+
+
+def crowd_reach(ref, trace):
+    """What the scene `crowd` is for, from the reference's record, the host path's step records and the scene's roles: every
+    count must be at least 1."""
+    import physics_scenes as ps
+    R, T = ps.CROWD_ROLES, ps.CROWD_SCRIPT_TICK
+    spec = ps.CROWD
+    friction = lambda role: spec["materials"][spec["sprites"][spec["objects"][R[role]]["sprite"]]["boxes"][0][2]]["friction"]  # noqa: E731
+    f_bar, f_low, f_high = friction("bar"), friction("block_low"), friction("block_high")
+    assert R["block_low"] < R["bar"] < TILE < R["block_high"] and f_low * f_bar != f_high * f_bar
+    assert R["taker_low"] < TILE <= R["giver"] < R["taker_high"] and R["mover_low"] < TILE < R["late_high"]
+    assert R["late_low"] < TILE <= R["mover_1024"]
+    r = dict.fromkeys(CROWD_REACH, 0)
+    for t, steps in enumerate(trace):
+        for k, s in steps:
+            if k == R["bar"] and s["blocked"]:
+                # the lower block's terms first, then the higher block's: each block's friction is its own
+                low, high = s["terms"].count(f_low * f_bar * 1.0), s["terms"].count(f_high * f_bar * 1.0)
+                fwd = rev = 0
+                for term in s["terms"]:
+                    fwd += term
+                for term in reversed(s["terms"]):
+                    rev += term
+                if low and high and low + high == len(s["terms"]) and s["terms"][:low] == [f_low * f_bar * 1.0] * low and fwd != rev:
+                    r["contacts_both_sides_one_step"] += 1
+            if k == R["giver"] and sum(0 < f < 1 for f in s["factors"]) >= 2:
+                before = ref["vel"][t - 1] if t else np.array([o["vel"] for o in spec["objects"]], np.float64)
+                took = [(ref["vel"][t][R[role]] != before[R[role]]).any() for role in ("taker_low", "taker_high")]
+                r["transfers_both_sides_one_step"] += all(took)
+            r["movers_from_1024"] += k >= TILE and not s["blocked"]
+    x, z = ref["pos"][:, R["mover_low"], 0], ref["pos"][:, R["mover_1024"], 2]
+    # late_high comes into view at the script's tick; mover_low, before it in the order, still moves on then and stops a tick later
+    seen = ref["visible"][:, R["late_high"]]
+    r["visible_before_met"] = int(not seen[T - 1] and seen[T] and x[T] > x[T - 1] and x[T + 1] == x[T])
+    # late_low likewise; mover_1024, after it in the order, stops at the script's tick
+    seen = ref["visible"][:, R["late_low"]]
+    r["visible_now_met"] = int(not seen[T - 1] and seen[T] and z[T - 1] > z[T - 2] and z[T] == z[T - 1])
+    return {k: int(v) for k, v in r.items()}
+
+
+def unchanged(path, out):
+    """The file at `path` already holds exactly the arrays `out`: it is left as it is (a zip archive carries the time of writing)."""
+    if not os.path.exists(path):
+        return False
+    z = np.load(path)
+    if sorted(z.files) != sorted(out):
+        return False
+    return all(z[k].dtype == np.asarray(v).dtype and z[k].shape == np.asarray(v).shape and z[k].tobytes() == np.asarray(v).tobytes()
+               for k, v in out.items())
+
+
 def main():
     import physics_scenes as ps
     data, lib, mod = load_reference()
@@ -177,6 +233,10 @@ def main():
             assert ref["weight"].tolist() == mod_weights, (ref["weight"].tolist(), mod_weights)
         r = reach(trace, counters)
         r["outside"] = len(outside)
+        if name == "crowd":
+            r.update(crowd_reach(ref, trace))
+            short = {k: r[k] for k in CROWD_REACH if r[k] < 1}
+            assert not short, "crowd does not reach what it is for: %r" % (r,)
         if name in ps.DEVICE_SCENES:
             dense, _, dense_counters = run_host(spec, dense=True)
             for k, v in ref.items():
@@ -192,6 +252,9 @@ def main():
     short = {k: (total[k], REACH[k]) for k in REACH if total[k] < REACH[k]}
     assert not short, "the scenes do not reach what they are for: %r" % (short,)
     for name, out in files.items():
+        if unchanged(ps.fixture_path(name), out):
+            print(os.path.relpath(ps.fixture_path(name), OUT), "unchanged")
+            continue
         np.savez_compressed(ps.fixture_path(name), **out)
         print(os.path.relpath(ps.fixture_path(name), OUT), os.path.getsize(ps.fixture_path(name)), "bytes")
 

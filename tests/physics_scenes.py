@@ -122,6 +122,48 @@ def _pile():
 
 PILE = _pile()
 
+# More bodies than one tile of the device's walk over them (vrt_physics.hip: VRT_PHYS_BLOCK = 1024 bodies at a time, the
+# validation loop strides alike).  CROWD_ROLES: where the bodies that matter stand in the physics order, on both sides of 1024.
+CROWD_N = 1100
+CROWD_ROLES = dict(block_low=1, bar=2, taker_low=5, mover_low=7, late_low=9, mover_1024=1024, block_high=1050, giver=1060,
+                   taker_high=1080, late_high=1090)
+CROWD_SCRIPT_TICK = 2
+
+
+def _crowd():
+    """1100 objects, 4 ticks, no gravity, everything within dist_max and dist_move of the camera but the two parked obstacles.
+    1090 static 2^3 dots stand on a lattice at y = -60, out of the way.  Every object starts with visible = False, so what a body
+    meets at a HIGHER index it meets from tick 1 on: the stations below play at ticks 1 to 3.
+      bar (2)         12 x 2 x 2 of friction 1, falls (tick 0: free; tick 1: one free step, then blocked) on block_low (1: two
+                      contacts of friction 1, terms 1.0) and block_high (1050: eight contacts of friction 2^-53) in one step: the
+                      sum is 2.0 in the order of the indices and 2 + 2^-50 the other way round
+      giver (1060)    a light 4^3 cube at 1.25 along x: at tick 1 its slab meets taker_low (5) and taker_high (1080) side by side,
+                      and both take velocity in the same step, by factors inside (0, 1)
+      mover_low (7)   a 4^3 cube at 1.5 along x; before tick 2 the script moves late_high (1090, parked out of sight) right in
+                      front of it: not yet visible for a mover BEFORE it in the order (last tick's flag), which moves on into it
+                      and is blocked at tick 3
+      mover_1024      a 4^3 cube at 1.5 along z; before tick 2 late_low (9) is moved in front of it: already visible for a mover
+                      AFTER it in the order (this tick's flag), which is blocked at tick 2"""
+    sprites = {"dot": full((2, 2, 2), 1), "dot0": full((2, 2, 2), 0), "dot2": full((2, 2, 2), 2), "dot3": full((2, 2, 2), 3),
+               "cube": full((4, 4, 4), 0), "cube2": full((4, 4, 4), 2), "bar": full((12, 2, 2), 3), "block4": full((4, 2, 2), 4)}
+    objects = [obj("dot", (-99 + 6 * (i % 34), -60, -99 + 6 * (i // 34)), physics=False) for i in range(CROWD_N)]
+    R = CROWD_ROLES
+    objects[R["block_low"]] = obj("dot3", (-5, 0, -1), physics=False)
+    objects[R["block_high"]] = obj("block4", (4, 0, 0), physics=False)
+    objects[R["bar"]] = obj("bar", (0, 4.5, 0), vel=(0, -1.5, 0))
+    objects[R["giver"]] = obj("cube2", (58.75, 0, 0), vel=(1.25, 0, 0))
+    objects[R["taker_low"]] = obj("dot0", (64, 0, -1))
+    objects[R["taker_high"]] = obj("dot2", (64, 0, 2))
+    objects[R["mover_low"]] = obj("cube", (-60, 0, 0), vel=(1.5, 0, 0))
+    objects[R["late_high"]] = obj("dot", (0, 2000, 0), physics=False)
+    objects[R["mover_1024"]] = obj("cube", (0, 0, 60), vel=(0, 0, 1.5))
+    objects[R["late_low"]] = obj("dot", (40, 2000, 0), physics=False)
+    script = {CROWD_SCRIPT_TICK: [["move", R["late_high"], [-54, 0, 0]], ["move", R["late_low"], [0, 0, 66]]]}
+    return scene(sprites, objects, 4, script=script, gravity=0.0, dist_max=512, dist_move=512)
+
+
+CROWD = _crowd()
+
 # mods/default/init.py:6-214: the physics properties of its materials, its sprites and where its objects stand
 DEFAULT_MATS = dict(stone_marble=mat(1, 0.0025, 0.125, 0), stone_light=mat(1, 0.0025, 0.25, 0), stone_gray=mat(1, 0.0025, 0.375, 0),
                     stone_dark=mat(1, 0.0025, 0.5, 0), metal=mat(1, 0.0025, 0.125, 0), material=mat(1, 0.0005, 0.5, 0),
@@ -153,7 +195,7 @@ def _default():
 DEFAULT = _default()
 
 # fixture file (tests/golden/physics_<name>.npz) -> scene
-SCENES = {"default": DEFAULT, "pile": PILE, "fraction": FRACTION, **{"edges_" + k: v for k, v in EDGES.items()}}
+SCENES = {"default": DEFAULT, "pile": PILE, "fraction": FRACTION, **{"edges_" + k: v for k, v in EDGES.items()}, "crowd": CROWD}
 DEVICE_SCENES = [n for n in SCENES if n != "fraction"]
 
 

@@ -7,7 +7,9 @@
 2. `expect`: vrt_surface records and the statistics words for arrays of records, validation included.
 3. `cases()`: the three scenes (gpu_util.sparse_scene, owner_ref.lod_world, the edge scene res9 at chunk size 32) with smooth
    materials whose ior is drawn from {0, 0.25, 0.5, 0.75, 1}, their rays, the first hits and the lives that end shade_ref.trace
-   with the step after the hit.  Built once, shared by the CPU and the GPU tests, never changed."""
+   with the step after the hit.  Built once, shared by the CPU and the GPU tests, never changed.
+4. `edge_case`, `lattice_case`: the same over the edge scenes of tests/edge_scenes.py -- with the ray sets of tests/edge_rays.py,
+   and with whole-number rays that end exactly on chunk faces."""
 import math
 
 import numpy as np
@@ -203,6 +205,13 @@ def case(name, rough=False):
         # the two one-voxel objects' material: above 0.5 the y neighbour is asked at +1, where the chunk at resolution 3 snaps it
         # back onto the hit voxel and the chunk above finds nothing -- the constructed record is then ambiguous (test_surface_host)
         mats[int(lw["truth"][-1][2]) - 1, 5] = 0.75
+    _cases[key] = _finish(base, mats, origins, vels, lives)
+    return _cases[key]
+
+
+def _finish(base, mats, origins, vels, lives):
+    """The common tail of case(), edge_case() and lattice_case(): the scene with the smooth materials, the first hits, the
+    truth and the lives that end shade_ref.trace one step after each hit."""
     sc = sr.with_materials(base, mats)
     radius = round(sc.chunk_size / 2)
     hits = cr.march_records(sc, radius, origins, vels, lives)
@@ -216,5 +225,117 @@ def case(name, rough=False):
                lives=np.array(lives, np.float64), hits=hits, end_lives=end_lives, truth=truth)
     for a in (out["origins"], out["vels"], out["lives"], hits, end_lives):
         a.setflags(write=False)
-    _cases[key] = out
     return out
+
+
+# ---- the edge scenes (tests/edge_scenes.py) --------------------------------------------------------------------------------
+_edge_cases, _lattice_cases = {}, {}
+
+
+def edge_names():
+    import edge_rays as er
+    return list(er.ALL_CASES)
+
+
+def edge_case(name):
+    """case()'s dict for a set of tests/edge_rays.py: the scene of edge_scenes.edge_scene(name) with smooth materials (seed
+    131 + the case's place in edge_rays.ALL_CASES) and the origins, velocities and lives of edge_rays.edge_ray_set(name) --
+    chunk sizes 8, 32 and 64, worlds 2^26 to 2^27 cells out, origins beside +-2^28, resolutions up to 9, a dense and a 0.5 %
+    grid.  (case("res9") is this for one scene, under its own seed.)"""
+    if name not in _edge_cases:
+        import edge_rays as er
+        base, st, has_bg, origins, vels, lives = er.edge_ray_set(name)[:6]
+        mats = smooth_materials(len(base.materials), 131 + er.ALL_CASES.index(name))
+        _edge_cases[name] = _finish(base, mats, origins, vels, lives)
+    return _edge_cases[name]
+
+
+LATTICE_CASES = ("fill_dense", "fill_sparse", "cs64", "far_pos", "far_neg", "far_mixed", "limit_28_pos", "limit_28_neg", "res9", "lod_full")
+LATTICE_RAYS = 400
+LATTICE_SCALES = (0.5, 1.0, 2.0, 3.0)
+
+
+def lattice_rays(sc, seed, n=LATTICE_RAYS):
+    """n rays that end exactly on chunk faces: whole-number origins `cell - d * k` (k in 1..6) in front of filled cells, with a
+    direction d of {-1, 0, 1}^3 less 0 scaled by one of LATTICE_SCALES, life 40.  The cells, by quota and in this order (a quota
+    no cell fills goes to the next): chunk corners (all three coordinates multiples of the chunk size); cells on the scene box's
+    lowest faces (a coordinate equal to the box's origin); cells in the box's last layer or on its highest chunk face (a
+    coordinate of the box's end less 1 or less a chunk size); cells with one or two coordinates on a chunk face; any cell.
+    In a scene with resolutions that do not divide a chunk face's coordinate the last fifth are upper_face_rays instead."""
+    import edge_rays as er
+    rng = np.random.default_rng(seed)
+    cs = sc.chunk_size
+    cells, _ = er.filled_cells(sc)
+    origin = np.asarray(sc.origin, np.int64)
+    end = origin + np.asarray(sc.dims, np.int64) * cs
+    on_face = (cells - origin) % cs == 0
+    pools = [np.flatnonzero(on_face.all(1)), np.flatnonzero((cells == origin).any(1)),
+             np.flatnonzero(((cells == end - 1) | (cells == end - cs)).any(1)), np.flatnonzero(on_face.any(1)), np.arange(len(cells))]
+    quotas = [n * 3 // 20, n // 4, n // 4, n // 4, n - n * 3 // 20 - 3 * (n // 4)]
+    pick, carry = [], 0
+    for pool, quota in zip(pools, quotas):
+        quota += carry
+        carry = 0
+        if len(pool) == 0:
+            carry = quota
+            continue
+        pick.append(pool[rng.integers(0, len(pool), quota)])
+    pick = np.concatenate(pick)
+    assert len(pick) == n
+    dirs = np.array([d for d in np.ndindex(3, 3, 3) if d != (1, 1, 1)], np.int64) - 1
+    d = dirs[rng.integers(0, len(dirs), n)]
+    k = rng.integers(1, 7, n)[:, None]
+    scale = np.array(LATTICE_SCALES)[rng.integers(0, len(LATTICE_SCALES), n)][:, None]
+    origins = (cells[pick] - d * k).astype(np.float64)
+    vels = d * scale
+    # where a chunk's resolution does not divide its upper face's coordinate (res9 alone among the edge scenes), the last fifth
+    # of the set goes to rays whose record only the chunk BELOW the one containing `cell` explains
+    faces = upper_face_rays(sc, rng)
+    m = min(n // 5, len(faces))
+    for i, (o, v) in enumerate(faces[:m]):
+        origins[n - m + i], vels[n - m + i] = o, v
+    return origins, vels, np.full(n, 40.0)
+
+
+def upper_face_rays(sc, rng):
+    """[(origin, velocity)], shuffled: unit rays along +a from one step (r cells) before the upper face F of a chunk of resolution
+    r with F % r != 0, anywhere in the r^3 cell of a filled voxel at (F // r) * r -- after one step the ray stands on F, still in
+    its chunk, and reads that voxel, while floor(pos) = F lies in the chunk above (owner_ref.lod_world aims its rays so)."""
+    cs = sc.chunk_size
+    out = []
+    for cell in np.argwhere(sc.present != 0):
+        r = int(sc.res[tuple(cell)])
+        cmin = np.asarray(sc.origin, np.int64) + cell * cs
+        lo = cell * cs
+        block = sc.grid[lo[0]:lo[0] + cs, lo[1]:lo[1] + cs, lo[2]:lo[2] + cs]
+        voxels = np.argwhere(block != 0) + cmin
+        voxels = voxels[(voxels % r == 0).all(1)]
+        for a in range(3):
+            face = int(cmin[a]) + cs
+            if face % r == 0 or face - r < cmin[a]:
+                continue
+            for q in voxels[voxels[:, a] == (face // r) * r]:
+                o = np.minimum(q + rng.integers(0, r, 3), cmin + cs - 1)
+                o[a] = face - r
+                v = np.zeros(3)
+                v[a] = 1.0
+                out.append((o.astype(np.float64), v))
+    return [out[i] for i in rng.permutation(len(out))]
+
+
+def lattice_case(name):
+    """case()'s dict for the lattice rays of an edge scene of LATTICE_CASES (smooth materials under seed 231 + its place there):
+    the hits whose `pos` is a whole multiple of the chunk size on one, two or three axes -- the candidates m = 1..7 of the chunk
+    rule, chunk indices -1 at the box's low faces, probes at index = dims past its high ones."""
+    if name not in _lattice_cases:
+        import edge_scenes as es
+        base = es.edge_scene(name)[0]
+        at = LATTICE_CASES.index(name)
+        origins, vels, lives = lattice_rays(base, 7000 + at)
+        _lattice_cases[name] = _finish(base, smooth_materials(len(base.materials), 231 + at), origins, vels, lives)
+    return _lattice_cases[name]
+
+
+def low_mask(sc, pos, cell):
+    """Bit a: pos[a] is a whole multiple of the chunk size (the record's `low` of the chunk rule), from a record alone."""
+    return sum(int(float(pos[a]) == float(int(cell[a])) and int(cell[a]) % sc.chunk_size == 0) << a for a in range(3))

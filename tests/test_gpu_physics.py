@@ -1,7 +1,8 @@
 """Object physics on the device (DeviceWorld.tick, vrt_physics_tick): every recorded run of the real reference
 (tests/golden/physics_*.npz) tick by tick and bit for bit, side by side with the host path (world.tick) including the per-body
 counts and the statistics; the tick between the existing passes (edit -> tick -> update -> render, owners); the kernel's model
-lookup through all 64 quarter-turn triples against the host world; what the device refuses, and that it touches nothing else."""
+lookup through all 64 quarter-turn triples against the host world; what the device refuses, and that it touches nothing else --
+also in the second tile of 1024 bodies, and at each limit's own value (the recorded scene `crowd` has 1100 bodies)."""
 import ctypes as C
 import os
 
@@ -240,22 +241,24 @@ def _raw_tick(bodies, models, remap, matphys, n_materials, params=(0.0, 1.0, 0.0
     return out, stats.cpu().numpy()
 
 
+def _body(pos, half, size, model, vel=(0, 0, 0), physics=1):
+    """A vrt_body record by hand: visible, awake, with a sprite, its box as Object.move leaves it."""
+    b = np.zeros((), np.dtype(nat.BODY_FIELDS))
+    b["pos"], b["vel"], b["weight"], b["half"] = pos, vel, 0.5, half
+    b["object"]["mins"] = [int(np.ceil(p)) - h for p, h in zip(pos, half)]
+    b["object"]["maxs"] = [int(np.floor(p)) + h for p, h in zip(pos, half)]
+    b["object"]["size"], b["object"]["model"], b["object"]["remap"] = size, model, 0
+    b["visible_before"] = b["visible_now"] = b["awake"] = b["has_sprite"] = 1
+    b["physics"], b["rim"] = physics, -1
+    return b
+
+
 def _hand_scene():
     """A 8 x 2 x 8 slab at the origin, a 2^3 cube one cell above it moving down, another flying free: the records, by hand."""
     models = np.ones(8 * 2 * 8 + 8, np.uint8)
     remap = np.array([0, 1], np.uint8)
     matphys = np.array([[0, 0, 0, 0], [1, 0.5, 0.25, 0]], np.float64)
-
-    def body(pos, half, size, model, vel=(0, 0, 0), physics=1):
-        b = np.zeros((), np.dtype(nat.BODY_FIELDS))
-        b["pos"], b["vel"], b["weight"], b["half"] = pos, vel, 0.5, half
-        b["object"]["mins"] = [int(np.ceil(p)) - h for p, h in zip(pos, half)]
-        b["object"]["maxs"] = [int(np.floor(p)) + h for p, h in zip(pos, half)]
-        b["object"]["size"], b["object"]["model"], b["object"]["remap"] = size, model, 0
-        b["visible_before"] = b["visible_now"] = b["awake"] = b["has_sprite"] = 1
-        b["physics"], b["rim"] = physics, -1
-        return b
-
+    body = _body
     slab = body((0, 0, 0), (4, 1, 4), (8, 2, 8), 0, physics=0)
     cube = body((0, 3, 0), (1, 1, 1), (2, 2, 2), 128, vel=(0, -1.5, 0))
     free = body((20, 0.5, 0), (1, 1, 1), (2, 2, 2), 128, vel=(0.75, 0, 0.75))
@@ -311,6 +314,122 @@ def test_refused_bodies_are_counted_and_untouched_and_their_neighbours_unaffecte
     assert out[valid].tobytes() == clean.tobytes()        # the neighbours did what they do without them
     assert stats[nat.S_PHYSICS_REFUSED] == len(bads) and stats[nat.S_PHYSICS_BODIES] == 2 and stats[nat.S_PHYSICS_CAPPED] == 0
     assert np.array_equal(np.delete(stats, nat.S_PHYSICS_REFUSED), np.delete(clean_stats, nat.S_PHYSICS_REFUSED))
+
+
+@gpu
+def test_refused_bodies_in_the_second_tile_of_the_walk():
+    """1030 records: the validation loop and the walk over the other bodies both take a second trip of 1024.  Refused bodies
+    at 1023, 1024 and 1029 (the last) stand where the cube at 1026 is going: they are untouched, counted and met by none, and the
+    valid bodies do exactly what they do in the same array without them."""
+    models, remap, matphys, slab, cube, free = _hand_scene()
+    n = 1030
+    far = [_body((1000 + 10 * i, 0, 0), (1, 1, 1), (2, 2, 2), 128, physics=0) for i in range(n)]
+    blocker = cube.copy()
+    blocker["pos"], blocker["vel"] = (0, 2, 0), (0, 0, 0)
+    blocker["object"]["mins"], blocker["object"]["maxs"] = [-1, 1, -1], [1, 3, 1]
+    bads = {1023: blocker.copy(), 1024: blocker.copy(), n - 1: blocker.copy()}
+    bads[1023]["pos"][0] = float("nan")
+    bads[1024]["vel"][2] = -2000.0
+    bads[n - 1]["object"]["model"] = -1
+    mixed = np.array(far)
+    mixed[0], mixed[2], mixed[1026] = slab, free, cube
+    for k, b in bads.items():
+        mixed[k] = b
+    valid = np.array([k for k in range(n) if k not in bads])
+    clean, clean_stats = _raw_tick(mixed[valid], models, remap, matphys, 1)
+    at = int(np.flatnonzero(valid == 1026)[0])
+    assert clean[at]["steps"] == 2 and clean[at]["blocked_steps"] == 1 and clean[at]["contacts"] == 4 and clean[at]["pos"].tolist() == [0, 2, 0]
+    assert clean_stats[nat.S_PHYSICS_BODIES] == 2 and clean_stats[nat.S_PHYSICS_REFUSED] == 0 and (clean["status"] != nat.BODY_REFUSED).all()
+    out, stats = _raw_tick(mixed, models, remap, matphys, 1)
+    for k in bads:
+        assert out[k]["status"] == nat.BODY_REFUSED, k
+        a, b = out[k].copy(), mixed[k].copy()
+        for f in ("steps", "blocked_steps", "contacts", "transfers", "moved", "status"):
+            assert f == "status" or out[k][f] == 0, (k, f)
+            a[f] = b[f] = 0
+        assert a.tobytes() == b.tobytes(), k              # but for the `out` words not a byte of a refused body changed
+    assert out[valid].tobytes() == clean.tobytes()
+    assert stats[nat.S_PHYSICS_REFUSED] == 3 and stats[nat.S_PHYSICS_CAPPED] == 0
+    assert np.array_equal(np.delete(stats, nat.S_PHYSICS_REFUSED), np.delete(clean_stats, nat.S_PHYSICS_REFUSED))
+    # were the blocker met it would stop the cube a step early: the same record, valid, at 1024
+    mixed[1024] = blocker
+    met, _ = _raw_tick(mixed, models, remap, matphys, 1)
+    assert met[1024]["status"] == nat.BODY_OK and met[1026]["pos"].tolist() == [0, 3, 0] and met[1026]["blocked_steps"] == 1
+
+
+def _header_define(name):
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    return int(re.search(r"^#define %s (\d+)\b" % name, open(os.path.join(root, "include", "vrt.h")).read(), re.M).group(1))
+
+
+@gpu
+def test_limits_accept_the_value_and_refuse_the_next():
+    """include/vrt.h's refusal limits, each at its value (accepted: skipped, as these bodies are not physical) and just beyond it
+    (refused): |vel| <= 1024, half <= 1024 with thin models of 2048 voxels along x and along y, a box extent <= 2049,
+    |pos| < 2^28."""
+    max_vel, max_half = _header_define("VRT_PHYSICS_MAX_VEL"), _header_define("VRT_PHYSICS_MAX_HALF")
+    assert (max_vel, max_half) == (1024, 1024)
+    models = np.ones(2 * max_half * 2 * 2, np.uint8)
+    remap = np.array([0, 1], np.uint8)
+    matphys = np.array([[0, 0, 0, 0], [1, 0.5, 0.25, 0]], np.float64)
+    cases = []                                                      # (what, the record at the limit, the record beyond it)
+
+    def pair(what, x, change_at, change_beyond, half=(1, 1, 1), size=(2, 2, 2)):
+        a, b = (_body((x, 0, 0), half, size, 0, physics=0) for _ in range(2))
+        change_at(a), change_beyond(b)
+        cases.append((what, a, b))
+
+    def setter(field, value, sub=None):
+        def apply(b):
+            (b["object"] if sub else b)[field] = value
+        return apply
+
+    for sign in (1.0, -1.0):
+        pair("vel %+d" % sign, 0, setter("vel", (0, sign * max_vel, 0)), setter("vel", (0, sign * np.nextafter(float(max_vel), np.inf), 0)))
+        pair("pos %+d" % sign, 10000, setter("pos", (sign * np.nextafter(2.0 ** 28, 0), 0, 0)), setter("pos", (sign * 2.0 ** 28, 0, 0)))
+    thin_x, thin_y = (max_half, 1, 1), (1, max_half, 1)
+    pair("half x", 20000, lambda b: None, setter("half", (max_half + 1, 1, 1)), half=thin_x, size=(2 * max_half, 2, 2))
+    pair("half y", 30000, lambda b: None, setter("half", (1, max_half + 1, 1)), half=thin_y, size=(2, 2 * max_half, 2))
+    pair("extent", 40000, setter("maxs", (40000 + max_half + 1, 1, 1), True), setter("maxs", (40000 + max_half + 2, 1, 1), True),
+         half=thin_x, size=(2 * max_half, 2, 2))
+    at_limit = np.array([a for _, a, _ in cases])
+    beyond = np.array([b for _, _, b in cases])
+    ext = at_limit["object"]["maxs"] - at_limit["object"]["mins"]
+    assert ext[4:6].max() == 2 * max_half and ext[6, 0] == 2 * max_half + 1
+    assert (beyond["object"]["maxs"] - beyond["object"]["mins"])[6, 0] == 2 * max_half + 2
+    both = np.concatenate([at_limit, beyond])
+    out, stats = _raw_tick(both, models, remap, matphys, 1)
+    for k, (what, _, _) in enumerate(cases):
+        assert out[k]["status"] == nat.BODY_SKIPPED, what
+        assert out[len(cases) + k]["status"] == nat.BODY_REFUSED, what
+    assert stats[nat.S_PHYSICS_REFUSED] == len(cases) and stats[nat.S_PHYSICS_BODIES] == 0
+    for f in ("pos", "vel", "half", "object"):
+        assert out[f].tobytes() == both[f].tobytes(), f
+
+
+@gpu
+def test_a_body_at_the_velocity_limit_takes_its_full_step_loop():
+    """|vel| = max_velocity = 1024 = VRT_PHYSICS_MAX_VEL: accepted; the body takes more than 1000 unit steps in one tick, far below
+    VRT_PHYSICS_STEP_CAP (3078, which accepted input cannot reach: 1024 steps of at most one unit each), and ends blocked on a
+    wall -- on the device as on the host, in position, velocity, counts and CAPPED = 0."""
+    spec = ps.scene({"cube": ps.full((2, 2, 2)), "wall": ps.full((2, 8, 8), 1)},
+                    [ps.obj("wall", (1010, 0, 0), physics=False), ps.obj("cube", (0, 0, 0), vel=(1024.0, 0, 0))], 0,
+                    gravity=0.0, friction_air=0.0, min_velocity=0.0, max_velocity=1024.0, dist_move=10 ** 6, dist_max=10 ** 6)
+    dev, _, _, st = ps.project_scene(spec)
+    host, _, _, _ = ps.project_scene(spec)
+    dw = DeviceWorld(8)
+    cam = vec3(0, 0, 0)
+    for k in range(2):
+        r = dw.tick(dev, cam, st)
+        want = world.tick(host, cam, st)
+        assert np.array_equal(r.counters, want), (k, r.counters, want)
+        assert ps.state(dev)["pos"].tobytes() == ps.state(host)["pos"].tobytes() and ps.state(dev)["vel"].tobytes() == ps.state(host)["vel"].tobytes()
+        assert int(r.stats[nat.S_PHYSICS_CAPPED]) == 0 and int(r.stats[nat.S_PHYSICS_REFUSED]) == 0
+        if k == 0:
+            # (the cube's leading layer, at model x = 1, meets the wall's first layer at world x = 1009 from pos.x = 1008)
+            assert 1000 < want[1]["steps"] < nat.PHYSICS_STEP_CAP // 2 and want[1]["blocked_steps"] == 1 and want[1]["contacts"] == 4
+            assert int(r.stats[nat.S_PHYSICS_STEPS]) == want[1]["steps"] and dev[1].pos.x == host[1].pos.x == 1008.0 and dev[1] in r.moved
 
 
 @gpu

@@ -70,6 +70,30 @@ def test_the_recorded_runs_reach_what_they_are_for():
     assert (z["pos"][-1, 3] != [-20, 0, 0]).any()
 
 
+def test_the_crowd_reaches_past_one_tile_of_bodies():
+    """The scene of more bodies than the device walks at a time (1024): what make_physics.py demanded of the reference's run,
+    from the file, and the record itself.  Measured: 3 blocked steps of the bar with contacts on both sides of index 1024, the
+    lower block's terms first, and a sum that depends on their order; 1 step that hands velocity to a body on either side; 12 free
+    steps of bodies at 1024 and beyond; both visibility cases."""
+    z, spec = ps.load_fixture("crowd")
+    R, T = ps.CROWD_ROLES, ps.CROWD_SCRIPT_TICK
+    assert len(spec["objects"]) == ps.CROWD_N >= 1024 + 64 and spec["ticks"] == 4
+    reached = json.loads(bytes(z["reached"]).decode())
+    for key in ("contacts_both_sides_one_step", "transfers_both_sides_one_step", "movers_from_1024", "visible_before_met", "visible_now_met"):
+        assert reached[key] >= 1, (key, reached)
+    # everything is in view from tick 0 on but the two parked obstacles, which the script brings in before tick T
+    late = [R["late_low"], R["late_high"]]
+    others = np.delete(np.arange(ps.CROWD_N), late)
+    assert z["visible"][:, others].all() and not z["visible"][:T, late].any() and z["visible"][T:, late].all()
+    # last tick's flag for the mover before the obstacle (it moves on at tick T, stops at T + 1), this tick's for the one after it
+    x, zz = z["pos"][:, R["mover_low"], 0], z["pos"][:, R["mover_1024"], 2]
+    assert x[T] > x[T - 1] and x[T + 1] == x[T] and zz[T - 1] > zz[T - 2] and zz[T] == zz[T - 1]
+    # the bar rests on both blocks from tick 1 on; both takers took velocity at tick 1
+    y = z["pos"][:, R["bar"], 1]
+    assert y[0] > y[1] == y[2] == y[3]
+    assert z["vel"][0, R["taker_high"], 0] == 0 and z["vel"][1, R["taker_high"], 0] > 0 and z["vel"][1, R["taker_low"], 0] > 0
+
+
 def test_fractional_solidity_follows_the_callers_draws():
     z, spec, counters = replay("fraction", seeded=True)
     assert spec["seed"] is not None and any(0 < m["solidity"] < 1 for m in spec["materials"])

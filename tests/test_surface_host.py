@@ -88,11 +88,13 @@ def test_hit_surfaces_rejects_bad_arguments_without_a_device():
 _checked = {}
 
 
-def checked(name):
-    """The case's reference records, each held to shade_ref.trace: dict(recs, stats, compared, skipped)."""
-    if name in _checked:
-        return _checked[name]
-    c = sf.case(name)
+def checked(name, kind="case"):
+    """The case's reference records, each held to shade_ref.trace: dict(recs, stats, compared, skipped).
+    kind: "case" (sf.case), "edge" (sf.edge_case) or "lattice" (sf.lattice_case)."""
+    key, name = (kind, name), (name if kind == "case" else "%s:%s" % (kind, name))
+    if key in _checked:
+        return _checked[key]
+    c = {"case": sf.case, "edge": sf.edge_case, "lattice": sf.lattice_case}[kind](key[1])
     sc = c["scene"]
     exp, stats, recs = sf.expect(sc, c["hits"], c["vels"])
     compared, skipped = 0, []
@@ -117,8 +119,8 @@ def checked(name):
         assert np.array_equal(np.array(rec["pos"]).view(np.uint64), np.array(s["next"]).view(np.uint64)), (name, k, rec["pos"], s["next"])
         assert (int(cnt[sr.C_NBR]), int(cnt[sr.C_CGET])) == (s["lookups"], s["fetches"]), (name, k, cnt, s)
         compared += 1
-    _checked[name] = dict(case=c, exp=exp, recs=recs, stats=stats, compared=compared, skipped=skipped)
-    return _checked[name]
+    _checked[key] = dict(case=c, exp=exp, recs=recs, stats=stats, compared=compared, skipped=skipped)
+    return _checked[key]
 
 
 @pytest.mark.parametrize("name", sf.CASES)
@@ -154,6 +156,89 @@ def test_cases_are_not_vacuous():
     lod = checked("lod")
     assert ambiguous >= 1 and lod["recs"][-1]["ambiguous"] and lod["skipped"] == [len(lod["recs"]) - 1]
     assert lod["recs"][-1]["chunk"] == (2, 1, 0) and lod["case"]["truth"][-1][3] == (1, 1, 0)
+
+
+EDGE_SETS = [("edge", n) for n in sf.edge_names()] + [("lattice", n) for n in sf.LATTICE_CASES]
+
+
+@pytest.mark.parametrize("kind,name", EDGE_SETS, ids=["%s-%s" % k for k in EDGE_SETS])
+def test_restatement_is_the_renderers_at_the_edges(kind, name):
+    """The same comparison over the edge scenes -- chunk sizes 8, 32 and 64, worlds 2^26 to 2^27 cells out, beside +-2^28,
+    resolutions up to 9, dense and 0.5 % grids -- with the rays of tests/edge_rays.py and with lattice rays that end on chunk
+    faces.  The explicit-ray calls' range rule rejects none of the rays, so the GPU tests can cast them."""
+    import edge_rays as er
+    got = checked(name, kind)
+    c = got["case"]
+    assert not er.rejected(c["scene"], c["origins"], c["vels"], c["lives"]).any()
+    hits = int((c["hits"]["material"] > 0).sum())
+    assert hits >= (20 if name in er.SMALL else 150) and got["compared"] + len(got["skipped"]) == hits, (hits, got["compared"])
+    assert len(got["skipped"]) <= int(got["stats"][nat.S_SURFACE_AMBIGUOUS])
+    assert int(got["stats"][nat.S_SURFACE_RESOLVED]) == hits == int(got["stats"][nat.S_SURFACE_EXAMINED])
+    assert int(got["stats"][nat.S_SURFACE_ORPHANS]) == 0 == int(got["stats"][nat.S_SURFACE_INVALID])
+
+
+def resolved(got):
+    return [(k, s) for k, s in enumerate(got["recs"]) if s["status"] == 0]
+
+
+def test_lattice_sets_reach_the_chunk_rules_low_candidates():
+    """From the reference alone: what the lattice sets are for.  Measured: records with a non-zero `low` mask per scene 133, 117,
+    143, 142, 143, 146, 124, 122, 177, 141 (in the order of sf.LATTICE_CASES); all three bits set 15; a candidate chunk at index
+    -1 759; the containing chunk at index = dims 38 (res9: hits read from the upper face of the box's last chunks, whose
+    resolution does not divide the face's coordinate); a neighbour probe at index = dims 9; records that a candidate m > 0
+    decides -- the containing chunk does not count, the chunk below does -- 73 (res9's upper-face rays: with resolutions 1 and 2
+    a chunk below can never count, its snapped voxel lies on the face itself)."""
+    all_bits = below = base_at_dims = probe_at_dims = decided_below = 0
+    for name in sf.LATTICE_CASES:
+        got = checked(name, "lattice")
+        c = got["case"]
+        sc = c["scene"]
+        cs, origin, dims = sc.chunk_size, [int(v) for v in sc.origin], [int(v) for v in sc.dims]
+        low_records = 0
+        for k, s in resolved(got):
+            pos, cell = c["hits"]["pos"][k], c["hits"]["cell"][k]
+            low = sf.low_mask(sc, pos, cell)
+            base = [(int(cell[a]) - origin[a]) // cs for a in range(3)]
+            low_records += low != 0
+            all_bits += low == 7
+            below += any((low >> a) & 1 and base[a] == 0 for a in range(3))            # the candidate one chunk below: index -1
+            base_at_dims += any(base[a] == dims[a] for a in range(3))
+            decided_below += tuple(s["chunk"]) != tuple(base)                           # a candidate m > 0 is the one that counts
+            # a neighbour probe that left the current chunk (`fetched`) for the cell one past the box's last chunk
+            probe = [np.floor(pos[a] + (1 if (s["side"] >> a) & 1 else -1)) for a in range(3)]
+            probe_at_dims += any((s["fetched"] >> a) & 1 and (int(probe[a]) - origin[a]) // cs == dims[a] for a in range(3))
+        print(name, "records with a low mask:", low_records)
+        assert low_records >= 50, (name, low_records)
+    print("all three bits", all_bits, "index -1", below, "containing chunk at dims", base_at_dims, "probe at dims", probe_at_dims,
+          "decided by a candidate below", decided_below)
+    assert decided_below >= 20
+    assert all_bits >= 5 and below >= 5 and probe_at_dims >= 5 and base_at_dims >= 1, (all_bits, below, base_at_dims, probe_at_dims)
+
+
+def test_edge_sets_reach_their_edges():
+    """From the reference alone.  Measured over the 21 sets: every reflect value (193 records and more each); 727 fetched bits; 520 enclosed records (227
+    of them fill_dense's); largest |pos| of a hit 67108991.9 (far_pos), 134217727.5 (far_neg), 268433372.5 and 268433371.2
+    (limit_28_pos / _neg); resolutions 1, 3 and 5 to 9 in res9."""
+    reflect = collections.Counter()
+    fetched = enclosed = 0
+    reach = {}
+    for name in sf.edge_names():
+        got = checked(name, "edge")
+        ok = resolved(got)
+        reflect.update(s["reflect"] for k, s in ok)
+        fetched += sum(bin(s["fetched"]).count("1") for k, s in ok)
+        enclosed += int(got["stats"][nat.S_SURFACE_ENCLOSED])
+        pos = got["case"]["hits"]["pos"][[k for k, s in ok]]
+        reach[name] = (float(pos.min()), float(pos.max()))
+    print("reflect", sorted(reflect.items()), "fetched bits", fetched, "enclosed", enclosed, "reach", reach)
+    assert set(reflect) == set(range(8)), reflect
+    assert fetched >= 100 and enclosed >= 200, (fetched, enclosed)
+    assert int(checked("fill_dense", "edge")["stats"][nat.S_SURFACE_ENCLOSED]) >= 200
+    # far_neg's box is [-2^27, -2^27 + 128) on x and y: its hits lie within a chunk or two of -2^27, beyond -2^27 + 192
+    assert reach["far_pos"][1] > 2.0 ** 26 and reach["far_neg"][0] < -(2.0 ** 27) + 192 and reach["far_neg"][0] < -(2.0 ** 26)
+    assert reach["limit_28_pos"][1] > 2.0 ** 28 - 4096 > 2.0 ** 27 and reach["limit_28_neg"][0] < -(2.0 ** 28) + 4096
+    assert {s["resolution"] for k, s in resolved(checked("res9", "edge"))} >= {1, 3, 5, 6, 7, 8, 9}
+    assert {checked(n, "edge")["case"]["scene"].chunk_size for n in ("far_mixed", "res9", "cs64")} == {8, 32, 64}
 
 
 # ---- 3. the normal -----------------------------------------------------------------------------------------------------------
