@@ -706,6 +706,9 @@ enum { VRT_S_PHYSICS_BODIES = 8,      /* bodies stepped (status 0) */
        VRT_S_PHYSICS_CONTACTS = 12,
        VRT_S_PHYSICS_TRANSFERS = 13,
        VRT_S_PHYSICS_CAPPED = 14      /* bodies whose step loop was ended by the iteration cap (below) */ };
+/* ... and the two more that vrt_physics_tick_draws writes. */
+enum { VRT_S_PHYSICS_RNG_INVALID = 7, /* 1 if the index word of d_rng was above 624: the tick did nothing */
+       VRT_S_PHYSICS_DRAWS = 15       /* random.random() calls of the tick */ };
 #define VRT_PHYSICS_MAX_VEL 1024       /* |vel|_inf above this: refused */
 #define VRT_PHYSICS_MAX_HALF 1024      /* half or a box extent beyond 2 * this + 1: refused */
 #define VRT_PHYSICS_STEP_CAP (3 * (VRT_PHYSICS_MAX_VEL + 2))
@@ -728,7 +731,8 @@ enum { VRT_S_PHYSICS_BODIES = 8,      /* bodies stepped (status 0) */
  *   d_matphys   [n_materials + 1][4] doubles by world material id: solidity, friction, elasticity, 0 (row 0 unused);
  *               d_remap[object.remap + model byte] is the id.  A material is SOLID iff solidity >= 1: `solidity >
  *               random.random()` is then always true, and for solidity <= 0 always false.  Fractional solidities need the
- *               draws in the reference's order and are the host path's (world.tick); the device treats them as not solid.
+ *               draws in the reference's order: vrt_physics_tick_draws (below) makes them; this call makes none and treats
+ *               such a material as not solid.
  *   d_stats     [VRT_NSTATS] uint64, zeroed by the callee: the VRT_S_PHYSICS_* words.
  * The bodies are device data, so each is validated on the device.  A body is REFUSED -- status -3, counted, neither moved nor
  * met, its velocity untouched -- when a pos or vel component or the weight is not finite, |pos[a]| >= 2^28, |vel[a]| > VRT_PHYSICS_MAX_VEL,
@@ -745,6 +749,26 @@ enum { VRT_S_PHYSICS_BODIES = 8,      /* bodies stepped (status 0) */
 int vrt_physics_tick(vrt_body* d_bodies, int32_t n_bodies, const uint8_t* d_models, int64_t models_bytes,
                      const uint8_t* d_remap, int32_t remap_bytes, const double* d_matphys, int32_t n_materials,
                      const vrt_physics_params* params, uint64_t* d_stats, void* stream);
+
+/* The same tick with the reference's random draws: every `solidity > random.random()` of data.py:537 (once for each slab voxel
+ * that holds a voxel of the neighbour) and data.py:539 (once more if that passed and the mover has a voxel there) is made from
+ * the caller's MT19937 state, in the reference's order -- bodies -> x -> y -> z, across passes, bodies, steps and ticks -- so a
+ * material of 0 < solidity < 1 is solid exactly where it is for the reference.  Materials of solidity >= 1 and <= 0 draw as well
+ * (their draws decide nothing and move the generator on); `solidity > draw` is a binary64 comparison, so a NaN solidity fails
+ * it after consuming its one draw.  A contact is (solidity_j > d1) && voxel of k && (solidity_k > d2).
+ *   d_rng       625 uint32 in device memory, 4-byte aligned: random.Random.getstate()[1] -- the 624 state words, then the index
+ *               of the next output in them, 0..624 (624: the state is twisted before the next output; odd values are legal: a
+ *               draw takes two outputs, which may lie in two successive states).  Read at the start of the call and written
+ *               back at its end: afterwards it is the state of a generator that has made the reference's draws -- CPython's
+ *               lazy regeneration, so a tick that ends on a state's last word hands that state back with index 624.
+ * The index is device data and is checked on the device before it is used: above 624 the tick does nothing -- every body gets
+ * status -3 and zeroed `out` words, nothing moves, d_rng is left as it is -- VRT_S_PHYSICS_RNG_INVALID is 1 and
+ * VRT_S_PHYSICS_REFUSED is n_bodies.  VRT_S_PHYSICS_DRAWS counts the draws.  Everything else -- records, refusals, limits,
+ * statistics, VRT_ERR_ARG -- is vrt_physics_tick's; VRT_ERR_ARG also for a NULL or misaligned (4 bytes) d_rng.  One launch of one
+ * workgroup, a kernel of its own (vrt_physics_tick's is unchanged); nothing is allocated or synchronised. */
+int vrt_physics_tick_draws(vrt_body* d_bodies, int32_t n_bodies, const uint8_t* d_models, int64_t models_bytes,
+                           const uint8_t* d_remap, int32_t remap_bytes, const double* d_matphys, int32_t n_materials,
+                           const vrt_physics_params* params, uint64_t* d_stats, uint32_t* d_rng, void* stream);
 
 /* Window.chunk_update's selection loop (init.py:447-452) on the device: which world chunks the camera renders this
  * frame and at which LOD.  The voxel blocks stay resident at full resolution; a chunk's LOD is only the resolution

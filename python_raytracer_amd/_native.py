@@ -22,7 +22,10 @@ SO_PATH = SO_OVERRIDE or os.path.join(HERE, ("_vrt_diaghist.so" if DIAG_HIST els
 UNITS = [os.path.join(HERE, "csrc", f) for f in ("vrt_kernels.hip", "vrt_surface.hip")]
 # the object physics (vrt_physics_tick) is a third unit of the same library, listed on its own
 PHYSICS_UNITS = [os.path.join(HERE, "csrc", "vrt_physics.hip")]
-SOURCES = UNITS + PHYSICS_UNITS + [os.path.join(HERE, "csrc", f) for f in ("vrt_math.h", "vrt_math_consts.h")]
+# ... and the tick that makes the reference's random draws (vrt_physics_tick_draws) a fourth, with a kernel of its own
+PHYSICS_DRAWS_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_draws.hip")]
+SOURCES = UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + \
+    [os.path.join(HERE, "csrc", f) for f in ("vrt_math.h", "vrt_math_consts.h", "vrt_physics_common.h")]
 SOURCES.append(os.path.join(ROOT, "include", "vrt.h"))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared"] + \
@@ -61,7 +64,7 @@ def build(force=False, verbose=False):
     """Compile python_raytracer_amd/_vrt.so for gfx950 (hipcc cross-compiles without a GPU)."""
     if not force and not needs_build():
         return SO_PATH
-    cmd = [HIPCC] + HIPCC_FLAGS + UNITS + PHYSICS_UNITS + ["-o", SO_PATH]
+    cmd = [HIPCC] + HIPCC_FLAGS + UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + ["-o", SO_PATH]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -190,6 +193,9 @@ class VrtPhysicsParams(C.Structure):
 # vrt_physics_tick only (VRT_S_PHYSICS_*): bodies stepped, refused, steps, blocked steps, contacts, transfers, iteration-cap hits
 S_PHYSICS_BODIES, S_PHYSICS_REFUSED, S_PHYSICS_STEPS, S_PHYSICS_BLOCKED = 8, 9, 10, 11
 S_PHYSICS_CONTACTS, S_PHYSICS_TRANSFERS, S_PHYSICS_CAPPED = 12, 13, 14
+# vrt_physics_tick_draws only: the index word of d_rng was out of range (the tick did nothing), random.random() calls of the tick
+S_PHYSICS_RNG_INVALID, S_PHYSICS_DRAWS = 7, 15
+RNG_WORDS = 625   # d_rng of vrt_physics_tick_draws: random.Random.getstate()[1]
 PHYSICS_MAX_VEL, PHYSICS_MAX_HALF, PHYSICS_STEP_CAP = 1024, 1024, 3 * (1024 + 2)
 
 _lib = None
@@ -297,6 +303,8 @@ def lib():
     L.vrt_stamp_model.argtypes = [vp, i64, i64, i64, C.POINTER(i32), vp, i32, vp]
     L.vrt_physics_tick.restype = C.c_int
     L.vrt_physics_tick.argtypes = [vp, i32, vp, i64, vp, i32, vp, i32, C.POINTER(VrtPhysicsParams), vp, vp]
+    L.vrt_physics_tick_draws.restype = C.c_int
+    L.vrt_physics_tick_draws.argtypes = [vp, i32, vp, i64, vp, i32, vp, i32, C.POINTER(VrtPhysicsParams), vp, vp, vp]
     L.vrt_canvas_blit.restype = C.c_int
     L.vrt_canvas_blit.argtypes = [vp, vp, i32, i32, vp, i64, vp]
     L.vrt_profile_begin.restype = C.c_int
@@ -331,7 +339,8 @@ EXPORTS = ["vrt_abi_version", "vrt_status_string", "vrt_last_hip_error", "vrt_de
            "vrt_pow_memo_create", "vrt_occupancy_build", "vrt_canvas_blit", "vrt_world_tables_bytes", "vrt_world_tables_build",
            "vrt_trace_workspace_bytes", "vrt_trace_rays", "vrt_rng_draws",
            "vrt_synth_volume", "vrt_profile_begin", "vrt_profile_begin_kinds", "vrt_profile_end", "vrt_select_chunks", "vrt_voxelize",
-           "vrt_hit_owners", "vrt_hit_surfaces", "vrt_edit_models", "vrt_stamp_model", "vrt_physics_tick"]
+           "vrt_hit_owners", "vrt_hit_surfaces", "vrt_edit_models", "vrt_stamp_model", "vrt_physics_tick",
+           "vrt_physics_tick_draws"]
 
 
 PLAN_FIELDS = ("launches", "pool", "wt_on", "trav_words", "bm_window", "ct_cells", "n_materials", "dyn_bytes", "static_bytes")

@@ -310,7 +310,9 @@ class PhysicsResult(_LazyStats):
     alone (steps, blocked_steps, contacts, transfers, moved, status: 0 stepped, -1 skipped, -3 refused) -- the array
     world.tick() returns for the same tick.  `kernel_ms`: the kernel's time if it was asked for, else None.
     `stats`: numpy int64[16], copied from the device on first use: word 8 = bodies stepped, 9 = refused, 10 = steps, 11 = blocked
-    steps, 12 = contacts, 13 = transfers, 14 = bodies the iteration cap ended."""
+    steps, 12 = contacts, 13 = transfers, 14 = bodies the iteration cap ended; of a tick with rng also 15 = random.random() calls,
+    which `draws` returns (0 for a tick without rng, which makes none), and 7 = 1 if the device found the generator's index out
+    of range and did nothing."""
 
     def __init__(self, records, moved, stats_dev, kernel_ms=None):
         from .world import PHYSICS_COUNTER_FIELDS
@@ -319,3 +321,8 @@ class PhysicsResult(_LazyStats):
         for name, *_ in PHYSICS_COUNTER_FIELDS:
             self.counters[name] = records[name]
         self._stats_dev = stats_dev
+
+    @property
+    def draws(self):
+        """The random.random() calls of the tick (word 15 of `stats`)."""
+        return int(self.stats[nat.S_PHYSICS_DRAWS])
