@@ -779,7 +779,9 @@ int vrt_physics_tick_draws(vrt_body* d_bodies, int32_t n_bodies, const uint8_t* 
  *   kept iff (!culling || chunk position was traversed in `prev`) (init.py:447); prev = the vrt_traversed box a
  *   previous vrt_render_tile filled (NULL or NULL keys: nothing traversed)
  *   lod = min(trunc(dist(chunk centre, cam_pos) / (dist_max / (1 + chunk_lod))), chunk_lod) (init.py:448-449),
- *   chunk centre = position + round(chunk_size / 2). */
+ *   chunk centre = position + round(chunk_size / 2); dist is the value CPython's math.dist returns for the two points
+ *   (the reference's vec3.distance; vrt_dist3 of vrt_math.h), bit for bit -- not sqrt(dx^2 + dy^2 + dz^2), which is an
+ *   ulp off on about one input in six and a whole LOD off where dist / step lands on an integer. */
 int vrt_select_chunks(const uint32_t* d_world_table, const int64_t* origin, const int32_t* dims, int32_t chunk_size,
                       const double* cam_pos, double dist_max, int32_t chunk_lod, int32_t culling,
                       const vrt_traversed* prev, uint32_t* d_camera_table, void* stream);

@@ -158,6 +158,9 @@ static libm_t libm_get(int mode) {
 double orc_sin(int mode, double x) { return libm_get(mode).sin_(x); }
 double orc_cos(int mode, double x) { return libm_get(mode).cos_(x); }
 double orc_pow(int mode, double x, double y) { return libm_get(mode).pow_(x, y); }
+/* vrt_math.h's math.dist of three differences (what orc_select_chunks and the HIP selection kernel call);
+ * tests/test_math.py holds it to CPython's known answers and to the correctly rounded value. */
+double orc_dist3(double dx, double dy, double dz) { return vrt_dist3(dx, dy, dz); }
 /* vrt_math.h's joint form of the lens quaternion's four values (what the HIP ray generation calls): out = sin a, cos a,
  * sin b, cos b; returns whether the straight-line fast block produced them.  tests/test_math.py holds it to vrt_sin /
  * vrt_cos bit for bit. */
@@ -638,7 +641,7 @@ void orc_select_chunks(const int64_t* origin, const int64_t* dims, int32_t cs, i
                 double dx = (double)(post[0] + chunk_radius) - cam_pos[0];
                 double dy = (double)(post[1] + chunk_radius) - cam_pos[1];
                 double dz = (double)(post[2] + chunk_radius) - cam_pos[2];
-                double dist = sqrt(dx * dx + dy * dy + dz * dz);
+                double dist = vrt_dist3(dx, dy, dz); /* vec3.distance is math.dist (lib.py:297-298) */
                 double q = trunc(dist / (dist_max / (double)(1 + chunk_lod)));
                 int lod = q < (double)chunk_lod ? (int)q : chunk_lod;
                 out_present[idx] = 1;

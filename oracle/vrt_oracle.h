@@ -86,7 +86,8 @@ int orc_render(const orc_scene* scene, const orc_settings* st, const orc_camera*
  * the camera iff (not culling or its position is in `traversed`), at LOD
  * min(trunc(dist(chunk centre, camera) / (dist_max / (1 + chunk_lod))), chunk_lod); Frame.resolution = lod + 1.
  * world_present / out_present / out_res: [dims0][dims1][dims2]; traversed: [n][3] chunk positions.
- * (math.dist is restated as sqrt(dx^2 + dy^2 + dz^2); the LOD index only depends on it through trunc().) */
+ * dist is math.dist's value (vrt_dist3 of vrt_math.h), not sqrt(dx^2 + dy^2 + dz^2): the two differ by an ulp on about one
+ * input in six, and trunc() turns that ulp into a whole LOD where dist / step lands on an integer. */
 void orc_select_chunks(const int64_t* origin, const int64_t* dims, int32_t chunk_size, int32_t chunk_radius,
                        const uint8_t* world_present, const double* cam_pos, double dist_max, int32_t chunk_lod,
                        int32_t culling, const int64_t* traversed, int64_t n_trav, uint8_t* out_present, uint8_t* out_res);
@@ -98,6 +99,8 @@ void orc_rng_draws(uint64_t seed_lo, uint64_t seed_hi, int n, double* out);
 double orc_sin(int libm_mode, double x);
 double orc_cos(int libm_mode, double x);
 double orc_pow(int libm_mode, double x, double y);
+/* math.dist((dx, dy, dz), (0, 0, 0)) by vrt_math.h's vrt_dist3 */
+double orc_dist3(double dx, double dy, double dz);
 
 /* number of samples of pixel (x, y) (init.py:131-134) */
 /* Window.draw_tile alpha-over blit (init.py:185-190); PARITY UNPINNED (pygame unavailable) */

@@ -356,7 +356,8 @@ class Camera:
             d = max(abs(lo - cam[a]), abs(hi - cam[a]))
             far2 += d * d
         q = math.sqrt(far2) / (float(s.dist_max) / (1 + lod_max))
-        # (one more than the formula's value guards the bound against the last rounding of the kernel's own square root)
+        # (the kernel's distance is math.dist's, bit for bit (vrt_dist3), while far2 sums the squares naively, and the farthest
+        # corner's centre may be no chunk's: the factor guards the bound against those last roundings, an ulp or two each)
         lod = min(int(math.trunc(q * (1 + 1e-12))), lod_max)
         return lod + 1
 

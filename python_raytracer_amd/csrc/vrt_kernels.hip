@@ -4261,7 +4261,7 @@ __global__ void __launch_bounds__(VRT_BLOCK) select_chunks_kernel(SelectParams S
         if (keep) {  // init.py:448-449
             const double dx = (double)(px + S.chunk_radius) - S.cam[0], dy = (double)(py + S.chunk_radius) - S.cam[1],
                          dz = (double)(pz + S.chunk_radius) - S.cam[2];
-            const double dist = __builtin_sqrt(dx * dx + dy * dy + dz * dz);
+            const double dist = vrt_dist3(dx, dy, dz);  // vec3.distance is math.dist (lib.py:297-298), not the naive root
             const double q = __builtin_trunc(dist / (S.dist_max / (double)(1 + S.chunk_lod)));
             const int lod = q < (double)S.chunk_lod ? (int)q : S.chunk_lod;
             e = slot | ((uint32_t)(lod + 1) << 24);

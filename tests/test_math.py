@@ -1,7 +1,9 @@
 """python_raytracer_amd/csrc/vrt_math.h (the sin / cos / pow the kernels and the oracle's portable mode share) against the
 correctly rounded value computed with mpmath at 300 bits, in the argument ranges the trace path uses:
 camera half-angles (|x| < 2 rad; lib.py:323-338 via init.py:41-43), (1 + bounces) ** (1 + falloff) (lib.py:450, 465).
-The header claims the correctly rounded result; glibc's own functions are only "< 1 ulp" and are counted beside it."""
+The header claims the correctly rounded result; glibc's own functions are only "< 1 ulp" and are counted beside it.
+vrt_dist3 (the chunk selection's distance, math.dist of lib.py:297-298) is held to CPython's known answers and to the
+correctly rounded distance, with the naive sqrt(dx*dx + dy*dy + dz*dz) counted beside it."""
 import ctypes as C
 
 import mpmath
@@ -21,6 +23,8 @@ def _lib():
         f.argtypes = [C.c_int, C.c_double]
     L.orc_pow.restype = C.c_double
     L.orc_pow.argtypes = [C.c_int, C.c_double, C.c_double]
+    L.orc_dist3.restype = C.c_double
+    L.orc_dist3.argtypes = [C.c_double, C.c_double, C.c_double]
     return L
 
 
@@ -103,3 +107,63 @@ def test_known_answers_from_cpython():
             else:
                 assert got == _correct(ref, *args), (name, args)
     assert n > 100 and same / n > 0.99, (n, same)
+
+
+def _kat_dist():
+    import gzip
+    import json
+    import os
+    with gzip.open(os.path.join(ol.GOLDEN, "kat_dist.json.gz"), "rt") as f:
+        kat = json.load(f)
+    return kat, {k: [[float.fromhex(v) for v in rec] for rec in recs] for k, recs in kat["vectors"].items()}
+
+
+def _naive_dist(dx, dy, dz):
+    return float(np.sqrt(np.float64(dx) * np.float64(dx) + np.float64(dy) * np.float64(dy) + np.float64(dz) * np.float64(dz)))
+
+
+def test_dist3_known_answers_from_cpython():
+    """tests/golden/kat_dist.json.gz: math.dist(chunk centre, camera) of the CPython that produced the golden fixtures
+    ([cx, cy, cz, px, py, pz, value] as hex floats; tests/golden/make_kat_dist.py), about 2,000 pairs in six families.
+    vrt_dist3 of the three rounded differences equals every value bit for bit; the naive formula misses the number of them
+    the generator counted, at least one in ten.  The expected values come from the file, never from this interpreter."""
+    kat, fam = _kat_dist()
+    assert kat["cpython"].startswith("3.") and set(fam) == {"integer", "far", "exact", "pythagorean", "boundary", "tiny"}
+    L = _lib()
+    n = naive_bad = 0
+    for name, vecs in fam.items():
+        assert len(vecs) >= 150, name
+        for cx, cy, cz, px, py, pz, want in vecs:
+            d = (cx - px, cy - py, cz - pz)
+            got = L.orc_dist3(*d)
+            assert got == want and not np.signbit(got), (name, [v.hex() for v in (cx, cy, cz, px, py, pz)], got.hex(), want.hex())
+            naive_bad += _naive_dist(*d) != want
+            n += 1
+    assert n >= 1900 and naive_bad == kat["naive_misses"] and naive_bad >= n // 10, (n, naive_bad)
+    # a difference's sign and order do not matter; zero differences never divide
+    assert L.orc_dist3(0.0, 0.0, 0.0) == 0.0 and L.orc_dist3(-0.0, 0.0, -3.0) == 3.0 and L.orc_dist3(3.0, -4.0, 0.0) == 5.0
+
+
+def test_dist3_is_correctly_rounded():
+    """vrt_dist3 against sqrt(dx^2 + dy^2 + dz^2) of the rounded differences, correctly rounded (mpmath, 300 bits), on the
+    kat_dist.json.gz pairs and 20,000 fresh ones: integer chunk centres against float cameras near the origin and 2^24 .. 2^28
+    cells out, cameras on halves, differences below 1.  The naive formula is counted beside it and misses thousands."""
+    _, fam = _kat_dist()
+    L = _lib()
+    rng = np.random.default_rng(14)
+    diffs = [(cx - px, cy - py, cz - pz) for vecs in fam.values() for cx, cy, cz, px, py, pz, _ in vecs]
+    c = np.concatenate([rng.integers(-320, 320, (N // 2, 3)) * 8 + 4,
+                        (rng.integers(1 << 21, 1 << 25, (N // 4, 3)) * 8 + 4) * rng.choice([-1, 1], (N // 4, 3)),
+                        rng.integers(-320, 320, (N // 4, 3)) * 8 + 4]).astype(np.float64)
+    p = np.concatenate([rng.uniform(-2600, 2600, (N // 2, 3)), c[N // 2:3 * N // 4] + rng.uniform(-300, 300, (N // 4, 3)),
+                        c[3 * N // 4:7 * N // 8] + rng.integers(-400, 400, (N // 8, 3)) / 2, c[7 * N // 8:] + rng.uniform(-1, 1, (N // 8, 3))])
+    assert len(c) == len(p) == N
+    diffs += [tuple(v) for v in (c - p).tolist()]
+    bad = naive_bad = 0
+    for dx, dy, dz in diffs:
+        m = [mpmath.mpf(v) for v in (dx, dy, dz)]
+        want = float(mpmath.sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]))
+        bad += L.orc_dist3(dx, dy, dz) != want
+        naive_bad += _naive_dist(dx, dy, dz) != want
+    assert bad == 0, (bad, naive_bad)
+    assert naive_bad > len(diffs) // 10, naive_bad
