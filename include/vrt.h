@@ -692,7 +692,7 @@ typedef struct vrt_body {
     int32_t moved;           /* out: 1 if the position changed (Object.move set redraw) */
     int32_t status;          /* out: 0 stepped; -1 skipped (not visible, asleep, not physical); -3 refused */
     int64_t rim;             /* in: offset in d_models of the plane [size.y][size.z] of model bytes at x = size.x, -1: empty (below) */
-    int32_t pad[2];
+    int32_t pad[2];          /* vrt_physics_run ORs into pad[0]: 1 = some tick moved the body, 2 = some tick changed its visibility */
 } vrt_body;
 enum { VRT_BODY_SKIPPED = -1, VRT_BODY_REFUSED = -3 };   /* vrt_body.status */
 typedef struct vrt_physics_params {
@@ -769,6 +769,65 @@ int vrt_physics_tick(vrt_body* d_bodies, int32_t n_bodies, const uint8_t* d_mode
 int vrt_physics_tick_draws(vrt_body* d_bodies, int32_t n_bodies, const uint8_t* d_models, int64_t models_bytes,
                            const uint8_t* d_remap, int32_t remap_bytes, const double* d_matphys, int32_t n_materials,
                            const vrt_physics_params* params, uint64_t* d_stats, uint32_t* d_rng, void* stream);
+
+/* Many ticks in one launch, the bodies resident throughout: `n_ticks` times `for obj in objects: obj.update(cam_pos)`, every tick
+ * bit for bit what vrt_physics_tick gives for the flags the host would have worked out for it, with the camera optionally
+ * re-attached to one body before every tick (init.py:464: cam.pos = data.player.cam_pos; data.py:614-618).
+ * What the host does around vrt_physics_tick happens on the device, at the START of every tick, from the positions as they
+ * are then (during a tick only a body's own physics moves it, and its flags are refreshed before its own physics runs):
+ *   camera      follow >= 0 and body `follow` is not refused at this tick: cam = pos[follow] + offset, componentwise, one
+ *               binary64 add each (offset: what Object.set_camera_pos adds for the body's rotation, which physics never
+ *               changes).  Otherwise the camera is `cam` as passed, at every such tick.
+ *   flags       for every body, refused ones included: visible_before = visible_now (what the tick before left; ON INPUT
+ *               visible_now holds Object.visible and visible_before and awake are ignored), dist = math.dist(pos, cam)
+ *               (vrt_dist3 of vrt_math.h), visible_now = has_sprite && dist <= dist_max + max(half), awake = dist <= dist_move.
+ *   validation  every body is validated anew against vrt_physics_tick's refusal rules: what can change between ticks -- pos,
+ *               vel, the box -- is judged as it is at this tick, so a body is refused (status -3, counted, neither moved nor
+ *               met, its velocity untouched) exactly at the ticks at which a fresh vrt_physics_tick would refuse it.
+ * Then the tick runs as vrt_physics_tick's: bodies in order, candidates compacted in order, transfers by one lane, slab voxel x
+ * candidate 1024 wide, contacts added serially in the reference's order, the step cap.  It makes no random draws: a material
+ * of fractional solidity is not solid, as for vrt_physics_tick.  After the call the `out` words of a body are its last tick's,
+ * the three flags are as the last tick set them, and pad[0] has been OR-ed with 1 if any tick moved the body and with 2 if any
+ * tick changed its visibility (the caller clears it before the first launch; vrt_physics_tick never touches it).
+ * ONE launch of ONE workgroup of 1024 threads with workgroup barriers only, as vrt_physics_tick: no grid barrier, no
+ * cooperative launch, nothing that waits on memory.  The launch ends in bounded time on any input: it counts WORK -- one unit
+ * per body turn, per step, and per pass of 1024 tests (flag refresh, box tests, voxel tests) -- and at the first tick boundary
+ * at or past run->budget it stops; VRT_S_PHYSICS_TICKS says how many ticks it did, at least one.  The caller continues with
+ * another launch on the same records (n_ticks less what was done, d_trace advanced by ticks done * n_bodies): chained launches
+ * leave every byte of the bodies and of the trace as one launch does, and the statistics add up.
+ *   d_trace     NULL, or [n_ticks][n_bodies] vrt_body_sample, 8-byte aligned: every body after every tick.
+ *   d_stats     [VRT_NSTATS] uint64, zeroed by the callee: the VRT_S_PHYSICS_* words of vrt_physics_tick as totals over the
+ *               ticks done (REFUSED counts a body once for each tick that refused it), VRT_S_PHYSICS_TICKS and _WORK.
+ * n_bodies = 0: nothing to do, VRT_S_PHYSICS_TICKS = n_ticks.  VRT_ERR_ARG, before any HIP call: whatever vrt_physics_tick
+ * refuses, NULL run, n_ticks < 1, budget < 1, follow outside [-1, n_bodies), cam, offset, dist_max or dist_move not finite,
+ * misaligned (8 bytes) d_trace.  Nothing is allocated or synchronised.  A kernel and a translation unit of its own
+ * (vrt_physics_tick's and vrt_physics_tick_draws's are unchanged). */
+typedef struct vrt_physics_run_params {
+    double  cam[3];          /* the camera where no body is followed (or the followed one is refused) */
+    double  offset[3];       /* camera = pos[follow] + offset */
+    double  dist_max;        /* settings.dist_max */
+    double  dist_move;       /* settings.dist_move: bodies further from the camera are asleep */
+    int64_t budget;          /* work units after which the launch stops at the next tick boundary (VRT_PHYSICS_RUN_BUDGET) */
+    int32_t n_ticks;
+    int32_t follow;          /* index of the body that carries the camera, -1: none */
+} vrt_physics_run_params;
+typedef struct vrt_body_sample {   /* 104 bytes: one body after one tick */
+    double  pos[3], vel[3];
+    int32_t mins[3], maxs[3];
+    int32_t visible;         /* visible_now of the tick */
+    int32_t awake;
+    int32_t out[6];          /* steps, blocked_steps, contacts, transfers, moved, status */
+} vrt_body_sample;
+enum { VRT_S_PHYSICS_WORK = 5,        /* work units counted (vrt_physics_run only) */
+       VRT_S_PHYSICS_TICKS = 6        /* ticks done by this launch (vrt_physics_run only) */ };
+/* The default budget.  A work unit costs 1.8 to 2.8 us on the MI355X (tools/bench_physics_run.py, profiles/physics_run_bench.json);
+ * 25 ms -- 50 ms with a factor of two to spare -- are 9028 units at the dearest, rounded down to a power of two: a launch lasts
+ * about 23 ms at the most, plus the rest of the tick in which the budget ran out. */
+#define VRT_PHYSICS_RUN_BUDGET 8192
+int vrt_physics_run(vrt_body* d_bodies, int32_t n_bodies, const uint8_t* d_models, int64_t models_bytes,
+                    const uint8_t* d_remap, int32_t remap_bytes, const double* d_matphys, int32_t n_materials,
+                    const vrt_physics_params* params, const vrt_physics_run_params* run, vrt_body_sample* d_trace,
+                    uint64_t* d_stats, void* stream);
 
 /* Window.chunk_update's selection loop (init.py:447-452) on the device: which world chunks the camera renders this
  * frame and at which LOD.  The voxel blocks stay resident at full resolution; a chunk's LOD is only the resolution

@@ -8,13 +8,13 @@ The compute path is the HIP library python_raytracer_amd/_vrt.so (include/vrt.h)
 """
 from . import data, lib
 from .data import Material, Frame, make_settings, load_settings, pixel_partition
-from .lib import vec3, quaternion, rgb, store, material, material_background
+from .lib import vec2, vec3, quaternion, rgb, store, material, material_background
 from .scene import PackedScene
 from .camera import Camera, RenderResult, HitResult, CastResult, ShadeResult, PathResult, SurfaceResult, release_caches
 from .canvas import Canvas
 from . import world
 from .world import OwnerResult
-from .results import PhysicsResult
+from .results import PhysicsResult, RunResult
 
-__all__ = ["Camera", "RenderResult", "HitResult", "CastResult", "ShadeResult", "PathResult", "SurfaceResult", "release_caches", "Canvas", "world", "OwnerResult", "PhysicsResult", "Material", "Frame", "PackedScene", "data", "lib", "vec3", "quaternion", "rgb",
+__all__ = ["Camera", "RenderResult", "HitResult", "CastResult", "ShadeResult", "PathResult", "SurfaceResult", "release_caches", "Canvas", "world", "OwnerResult", "PhysicsResult", "RunResult", "Material", "Frame", "PackedScene", "data", "lib", "vec2", "vec3", "quaternion", "rgb",
            "store", "material", "material_background", "make_settings", "load_settings", "pixel_partition"]

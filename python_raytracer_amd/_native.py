@@ -24,7 +24,9 @@ UNITS = [os.path.join(HERE, "csrc", f) for f in ("vrt_kernels.hip", "vrt_surface
 PHYSICS_UNITS = [os.path.join(HERE, "csrc", "vrt_physics.hip")]
 # ... and the tick that makes the reference's random draws (vrt_physics_tick_draws) a fourth, with a kernel of its own
 PHYSICS_DRAWS_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_draws.hip")]
-SOURCES = UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + \
+# ... and many ticks in one launch (vrt_physics_run) a fifth, again with a kernel of its own
+PHYSICS_RUN_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_run.hip")]
+SOURCES = UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + PHYSICS_RUN_UNITS + \
     [os.path.join(HERE, "csrc", f) for f in ("vrt_math.h", "vrt_math_consts.h", "vrt_physics_common.h")]
 SOURCES.append(os.path.join(ROOT, "include", "vrt.h"))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -64,7 +66,7 @@ def build(force=False, verbose=False):
     """Compile python_raytracer_amd/_vrt.so for gfx950 (hipcc cross-compiles without a GPU)."""
     if not force and not needs_build():
         return SO_PATH
-    cmd = [HIPCC] + HIPCC_FLAGS + UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + ["-o", SO_PATH]
+    cmd = [HIPCC] + HIPCC_FLAGS + UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + PHYSICS_RUN_UNITS + ["-o", SO_PATH]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -198,6 +200,30 @@ S_PHYSICS_RNG_INVALID, S_PHYSICS_DRAWS = 7, 15
 RNG_WORDS = 625   # d_rng of vrt_physics_tick_draws: random.Random.getstate()[1]
 PHYSICS_MAX_VEL, PHYSICS_MAX_HALF, PHYSICS_STEP_CAP = 1024, 1024, 3 * (1024 + 2)
 
+
+class VrtPhysicsRunParams(C.Structure):
+    """vrt_physics_run_params (include/vrt.h): the camera, its attachment, the two distances, the work budget and the ticks of
+    one vrt_physics_run launch, 80 bytes."""
+    _fields_ = [("cam", C.c_double * 3), ("offset", C.c_double * 3), ("dist_max", C.c_double), ("dist_move", C.c_double),
+                ("budget", C.c_int64), ("n_ticks", C.c_int32), ("follow", C.c_int32)]
+
+
+class VrtBodySample(C.Structure):
+    """vrt_body_sample (include/vrt.h): one body after one tick of vrt_physics_run, 104 bytes."""
+    _fields_ = [("pos", C.c_double * 3), ("vel", C.c_double * 3), ("mins", C.c_int32 * 3), ("maxs", C.c_int32 * 3),
+                ("visible", C.c_int32), ("awake", C.c_int32), ("out", C.c_int32 * 6)]
+
+
+# (the six `out` words by name: PHYSICS_COUNTER_FIELDS of world.py)
+BODY_SAMPLE_FIELDS = [("pos", "<f8", 3), ("vel", "<f8", 3), ("mins", "<i4", 3), ("maxs", "<i4", 3), ("visible", "<i4"), ("awake", "<i4"),
+                      ("steps", "<i4"), ("blocked_steps", "<i4"), ("contacts", "<i4"), ("transfers", "<i4"), ("moved", "<i4"),
+                      ("status", "<i4")]
+BODY_SAMPLE_BYTES = 104
+# vrt_physics_run only: work units counted, ticks done by the launch
+S_PHYSICS_WORK, S_PHYSICS_TICKS = 5, 6
+BODY_EVER_MOVED, BODY_EVER_FLIPPED = 1, 2   # vrt_body.pad[0] after vrt_physics_run
+PHYSICS_RUN_BUDGET = 1 << 13   # VRT_PHYSICS_RUN_BUDGET: about 23 ms of the dearest measured work units (DESIGN.md section 6f)
+
 _lib = None
 
 
@@ -305,6 +331,9 @@ def lib():
     L.vrt_physics_tick.argtypes = [vp, i32, vp, i64, vp, i32, vp, i32, C.POINTER(VrtPhysicsParams), vp, vp]
     L.vrt_physics_tick_draws.restype = C.c_int
     L.vrt_physics_tick_draws.argtypes = [vp, i32, vp, i64, vp, i32, vp, i32, C.POINTER(VrtPhysicsParams), vp, vp, vp]
+    L.vrt_physics_run.restype = C.c_int
+    L.vrt_physics_run.argtypes = [vp, i32, vp, i64, vp, i32, vp, i32, C.POINTER(VrtPhysicsParams), C.POINTER(VrtPhysicsRunParams),
+                                  vp, vp, vp]
     L.vrt_canvas_blit.restype = C.c_int
     L.vrt_canvas_blit.argtypes = [vp, vp, i32, i32, vp, i64, vp]
     L.vrt_profile_begin.restype = C.c_int
@@ -340,7 +369,7 @@ EXPORTS = ["vrt_abi_version", "vrt_status_string", "vrt_last_hip_error", "vrt_de
            "vrt_trace_workspace_bytes", "vrt_trace_rays", "vrt_rng_draws",
            "vrt_synth_volume", "vrt_profile_begin", "vrt_profile_begin_kinds", "vrt_profile_end", "vrt_select_chunks", "vrt_voxelize",
            "vrt_hit_owners", "vrt_hit_surfaces", "vrt_edit_models", "vrt_stamp_model", "vrt_physics_tick",
-           "vrt_physics_tick_draws"]
+           "vrt_physics_tick_draws", "vrt_physics_run"]
 
 
 PLAN_FIELDS = ("launches", "pool", "wt_on", "trav_words", "bm_window", "ct_cells", "n_materials", "dyn_bytes", "static_bytes")

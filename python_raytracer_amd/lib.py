@@ -23,6 +23,28 @@ class store:
         return "store(%s)" % ", ".join("%s=%r" % kv for kv in self.__dict__.items())
 
 
+class vec2:
+    """(reference lib.py:13-66) -- only what Object.set_camera needs of it: the two members and the comparison with 0."""
+    __slots__ = ("x", "y")
+
+    def __init__(self, x, y):
+        self.x, self.y = x, y
+
+    def __eq__(self, o):
+        if isinstance(o, vec2):
+            return (self.x, self.y) == (o.x, o.y)
+        return self.x == o and self.y == o
+
+    def __ne__(self, o):
+        return not self.__eq__(o)
+
+    def __hash__(self):
+        return hash((self.x, self.y))
+
+    def __repr__(self):
+        return "vec2(%r, %r)" % (self.x, self.y)
+
+
 class vec3:
     __slots__ = ("x", "y", "z")
 

@@ -326,3 +326,33 @@ class PhysicsResult(_LazyStats):
     def draws(self):
         """The random.random() calls of the tick (word 15 of `stats`)."""
         return int(self.stats[nat.S_PHYSICS_DRAWS])
+
+
+class RunResult(_LazyStats):
+    """What DeviceWorld.run() did.  `records`: the body records after the last tick, a numpy structured array of vrt_body
+    (include/vrt.h), one per object; their `out` fields are the last tick's (`counters`, as PhysicsResult's), and pad[0] says
+    whether any tick moved the body (1) or changed its visibility (2).  `moved`: the Objects whose position changed during the
+    run, in physics order.  `ticks_run`: the ticks done, always the ticks asked for; `launches`: the device launches they took
+    (more than one where the work budget ended a launch early).  `kernel_ms`: the launches' summed time if it was asked for.
+    `stats`: numpy int64[16], copied from the device on first use, summed over the launches: word 8 = body turns stepped,
+    9 = refusals (a body counts once per tick that refused it), 10 = steps, 11 = blocked steps, 12 = contacts, 13 = transfers,
+    14 = step loops the iteration cap ended, 5 = work units counted, 6 = ticks done.
+    `trace`: None, or with trace=True a numpy structured array [ticks][n] of _native.BODY_SAMPLE_FIELDS -- every body after
+    every tick -- copied from the device on first use."""
+
+    def __init__(self, records, moved, stats_dev, ticks_run, launches, trace_dev, trace_shape, kernel_ms=None):
+        from .world import PHYSICS_COUNTER_FIELDS
+        self.records, self.moved, self.kernel_ms = records, moved, kernel_ms
+        self.ticks_run, self.launches = ticks_run, launches
+        self.counters = np.zeros(len(records), np.dtype(PHYSICS_COUNTER_FIELDS))
+        for name, *_ in PHYSICS_COUNTER_FIELDS:
+            self.counters[name] = records[name]
+        self._stats_dev = stats_dev
+        self._trace_dev, self._trace_shape, self._trace = trace_dev, trace_shape, None
+
+    @property
+    def trace(self):
+        if self._trace is None and self._trace_dev is not None:
+            self._trace = self._trace_dev.cpu().numpy().view(np.dtype(nat.BODY_SAMPLE_FIELDS)).reshape(self._trace_shape)
+            self._trace_dev = None
+        return self._trace
