@@ -692,7 +692,7 @@ typedef struct vrt_body {
     int32_t moved;           /* out: 1 if the position changed (Object.move set redraw) */
     int32_t status;          /* out: 0 stepped; -1 skipped (not visible, asleep, not physical); -3 refused */
     int64_t rim;             /* in: offset in d_models of the plane [size.y][size.z] of model bytes at x = size.x, -1: empty (below) */
-    int32_t pad[2];          /* vrt_physics_run ORs into pad[0]: 1 = some tick moved the body, 2 = some tick changed its visibility */
+    int32_t pad[2];          /* vrt_physics_run ORs into pad[0]: 1 = some tick moved the body, 2 = some tick changed its visibility; vrt_physics_run_anim also 4 = some tick's anim_update changed the frame at its turn */
 } vrt_body;
 enum { VRT_BODY_SKIPPED = -1, VRT_BODY_REFUSED = -3 };   /* vrt_body.status */
 typedef struct vrt_physics_params {
@@ -828,6 +828,54 @@ int vrt_physics_run(vrt_body* d_bodies, int32_t n_bodies, const uint8_t* d_model
                     const uint8_t* d_remap, int32_t remap_bytes, const double* d_matphys, int32_t n_materials,
                     const vrt_physics_params* params, const vrt_physics_run_params* run, vrt_body_sample* d_trace,
                     uint64_t* d_stats, void* stream);
+
+/* vrt_physics_run with the sprites animated (Sprite.anim_update, data.py:304-306, as Object.update calls it: data.py:575-582):
+ * the same launch, the same tick, and at body k's turn -- after its flags are known, before its physics -- the switch of its
+ * sprite's frame.  The frame is state of the SPRITE: the first body of a tick that is not refused, visible_now and awake and
+ * shows sprite s switches s for every body that shows it; bodies earlier in the order have met the old frame in that tick, the
+ * later ones meet the new one.  Only the switching body gets the new frame's weight; the others keep theirs.
+ *   d_body_sprite  [n_bodies] index into d_sprites; negative or >= n_sprites: the body shows no animated sprite.
+ *   d_sprites      [n_sprites] in, out: `frame` is the sprite's current frame, and is where the run left it afterwards.
+ *   d_frames       [n_frame_rows]: frame f of sprite s is row d_sprites[s].first_row + f -- where its model and its rim plane lie
+ *                  in d_models, its base in d_remap and Object.set_weight's sum for it.
+ *   d_schedule     [n_ticks][n_sprites]: the frame anim_update sets at that tick (worked out by the host: CPython's float //
+ *                  and % stay off the device); a value outside [0, n_frames), -1 for one, changes nothing.  A chained launch
+ *                  passes the pointer advanced by ticks done * n_sprites, as it does d_trace.
+ *   d_anim_trace   NULL, or [n_ticks][n_bodies] vrt_anim_sample, 8-byte aligned, advanced like d_trace.
+ * The switch, when schedule[t][s] is a frame of s other than the current one: d_sprites[s].frame is set, body k takes the row's
+ * weight and 4 is OR-ed into its pad[0], and all 1024 threads walk the bodies: every body that shows s gets object.model,
+ * object.remap and rim from the row and is validated at once as at the start of a tick -- a row whose model, rim or remap base
+ * leaves the buffers gets those bodies refused (status -3, counted) from that moment of the tick on, and nothing is read out of
+ * bounds.  One work unit per 1024 bodies of such a walk.  A sprite whose rows leave [0, n_frame_rows) is never switched (the
+ * tables are device memory: the kernel checks this, the entry point cannot).
+ * n_sprites = 0: every byte as vrt_physics_run leaves it.  VRT_ERR_ARG, before any HIP call: whatever vrt_physics_run refuses,
+ * n_sprites or n_frame_rows negative, and while n_sprites > 0: NULL d_sprites or d_schedule, NULL d_body_sprite with bodies,
+ * NULL d_frames with rows, a misaligned array (4 bytes; d_frames and d_anim_trace 8).  A kernel and a translation unit of its
+ * own; the three other physics kernels are unchanged. */
+typedef struct vrt_anim_sprite {   /* 16 bytes */
+    int32_t frame;           /* in, out: Sprite.frame */
+    int32_t n_frames;
+    int32_t first_row;       /* row of frame 0 in d_frames */
+    int32_t pad;
+} vrt_anim_sprite;
+typedef struct vrt_anim_frame {    /* 32 bytes */
+    int64_t model;           /* vrt_object.model of a body that shows the frame */
+    int64_t rim;             /* vrt_body.rim */
+    int32_t remap;           /* vrt_object.remap */
+    int32_t pad;
+    double  weight;          /* Object.set_weight's sum over the frame */
+} vrt_anim_frame;
+typedef struct vrt_anim_sample {   /* 16 bytes: one body after one tick */
+    double  weight;
+    int32_t frame;           /* its sprite's frame, -1 if it shows no animated sprite */
+    int32_t switched;        /* 1 if this body made the switch at this tick */
+} vrt_anim_sample;
+int vrt_physics_run_anim(vrt_body* d_bodies, int32_t n_bodies, const uint8_t* d_models, int64_t models_bytes,
+                         const uint8_t* d_remap, int32_t remap_bytes, const double* d_matphys, int32_t n_materials,
+                         const vrt_physics_params* params, const vrt_physics_run_params* run, vrt_body_sample* d_trace,
+                         uint64_t* d_stats, void* stream, const int32_t* d_body_sprite, vrt_anim_sprite* d_sprites,
+                         int32_t n_sprites, const vrt_anim_frame* d_frames, int32_t n_frame_rows, const int32_t* d_schedule,
+                         vrt_anim_sample* d_anim_trace);
 
 /* Window.chunk_update's selection loop (init.py:447-452) on the device: which world chunks the camera renders this
  * frame and at which LOD.  The voxel blocks stay resident at full resolution; a chunk's LOD is only the resolution

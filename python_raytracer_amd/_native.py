@@ -26,7 +26,9 @@ PHYSICS_UNITS = [os.path.join(HERE, "csrc", "vrt_physics.hip")]
 PHYSICS_DRAWS_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_draws.hip")]
 # ... and many ticks in one launch (vrt_physics_run) a fifth, again with a kernel of its own
 PHYSICS_RUN_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_run.hip")]
-SOURCES = UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + PHYSICS_RUN_UNITS + \
+# ... and that run with the sprites animated (vrt_physics_run_anim) a sixth, again with a kernel of its own
+PHYSICS_ANIM_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_anim.hip")]
+SOURCES = UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + PHYSICS_RUN_UNITS + PHYSICS_ANIM_UNITS + \
     [os.path.join(HERE, "csrc", f) for f in ("vrt_math.h", "vrt_math_consts.h", "vrt_physics_common.h")]
 SOURCES.append(os.path.join(ROOT, "include", "vrt.h"))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -66,7 +68,7 @@ def build(force=False, verbose=False):
     """Compile python_raytracer_amd/_vrt.so for gfx950 (hipcc cross-compiles without a GPU)."""
     if not force and not needs_build():
         return SO_PATH
-    cmd = [HIPCC] + HIPCC_FLAGS + UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + PHYSICS_RUN_UNITS + ["-o", SO_PATH]
+    cmd = [HIPCC] + HIPCC_FLAGS + UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + PHYSICS_RUN_UNITS + PHYSICS_ANIM_UNITS + ["-o", SO_PATH]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -222,7 +224,30 @@ BODY_SAMPLE_BYTES = 104
 # vrt_physics_run only: work units counted, ticks done by the launch
 S_PHYSICS_WORK, S_PHYSICS_TICKS = 5, 6
 BODY_EVER_MOVED, BODY_EVER_FLIPPED = 1, 2   # vrt_body.pad[0] after vrt_physics_run
+BODY_EVER_SWITCHED = 4   # ... after vrt_physics_run_anim: some tick's anim_update changed the frame at this body's turn
 PHYSICS_RUN_BUDGET = 1 << 13   # VRT_PHYSICS_RUN_BUDGET: about 23 ms of the dearest measured work units
+
+
+
+class VrtAnimSprite(C.Structure):
+    """vrt_anim_sprite (include/vrt.h): one animated sprite of vrt_physics_run_anim, 16 bytes."""
+    _fields_ = [("frame", C.c_int32), ("n_frames", C.c_int32), ("first_row", C.c_int32), ("pad", C.c_int32)]
+
+
+class VrtAnimFrame(C.Structure):
+    """vrt_anim_frame (include/vrt.h): where one frame of an animated sprite lies on the device and what it weighs, 32 bytes."""
+    _fields_ = [("model", C.c_int64), ("rim", C.c_int64), ("remap", C.c_int32), ("pad", C.c_int32), ("weight", C.c_double)]
+
+
+class VrtAnimSample(C.Structure):
+    """vrt_anim_sample (include/vrt.h): one body's animation state after one tick of vrt_physics_run_anim, 16 bytes."""
+    _fields_ = [("weight", C.c_double), ("frame", C.c_int32), ("switched", C.c_int32)]
+
+
+ANIM_SPRITE_FIELDS = [("frame", "<i4"), ("n_frames", "<i4"), ("first_row", "<i4"), ("pad", "<i4")]
+ANIM_FRAME_FIELDS = [("model", "<i8"), ("rim", "<i8"), ("remap", "<i4"), ("pad", "<i4"), ("weight", "<f8")]
+ANIM_SAMPLE_FIELDS = [("weight", "<f8"), ("frame", "<i4"), ("switched", "<i4")]
+ANIM_SPRITE_BYTES, ANIM_FRAME_BYTES, ANIM_SAMPLE_BYTES = 16, 32, 16
 
 _lib = None
 
@@ -334,6 +359,8 @@ def lib():
     L.vrt_physics_run.restype = C.c_int
     L.vrt_physics_run.argtypes = [vp, i32, vp, i64, vp, i32, vp, i32, C.POINTER(VrtPhysicsParams), C.POINTER(VrtPhysicsRunParams),
                                   vp, vp, vp]
+    L.vrt_physics_run_anim.restype = C.c_int
+    L.vrt_physics_run_anim.argtypes = L.vrt_physics_run.argtypes + [vp, vp, i32, vp, i32, vp, vp]
     L.vrt_canvas_blit.restype = C.c_int
     L.vrt_canvas_blit.argtypes = [vp, vp, i32, i32, vp, i64, vp]
     L.vrt_profile_begin.restype = C.c_int
@@ -369,7 +396,7 @@ EXPORTS = ["vrt_abi_version", "vrt_status_string", "vrt_last_hip_error", "vrt_de
            "vrt_trace_workspace_bytes", "vrt_trace_rays", "vrt_rng_draws",
            "vrt_synth_volume", "vrt_profile_begin", "vrt_profile_begin_kinds", "vrt_profile_end", "vrt_select_chunks", "vrt_voxelize",
            "vrt_hit_owners", "vrt_hit_surfaces", "vrt_edit_models", "vrt_stamp_model", "vrt_physics_tick",
-           "vrt_physics_tick_draws", "vrt_physics_run"]
+           "vrt_physics_tick_draws", "vrt_physics_run", "vrt_physics_run_anim"]
 
 
 PLAN_FIELDS = ("launches", "pool", "wt_on", "trav_words", "bm_window", "ct_cells", "n_materials", "dyn_bytes", "static_bytes")

@@ -338,9 +338,14 @@ class RunResult(_LazyStats):
     9 = refusals (a body counts once per tick that refused it), 10 = steps, 11 = blocked steps, 12 = contacts, 13 = transfers,
     14 = step loops the iteration cap ended, 5 = work units counted, 6 = ticks done.
     `trace`: None, or with trace=True a numpy structured array [ticks][n] of _native.BODY_SAMPLE_FIELDS -- every body after
-    every tick -- copied from the device on first use."""
+    every tick -- copied from the device on first use.
+    With clock= (the sprites animated): pad[0] of a record also says whether some tick's anim_update changed the frame at that
+    body's turn (4); `frames`: {Sprite: its frame after the run} for every animated sprite (None without clock); `anim`: None,
+    or with trace=True a numpy structured array [ticks][n] of _native.ANIM_SAMPLE_FIELDS -- every body's weight after every
+    tick, its sprite's frame (-1: not animated) and whether the body made the switch at that tick."""
 
-    def __init__(self, records, moved, stats_dev, ticks_run, launches, trace_dev, trace_shape, kernel_ms=None):
+    def __init__(self, records, moved, stats_dev, ticks_run, launches, trace_dev, trace_shape, kernel_ms=None, frames=None,
+                 anim_dev=None):
         from .world import PHYSICS_COUNTER_FIELDS
         self.records, self.moved, self.kernel_ms = records, moved, kernel_ms
         self.ticks_run, self.launches = ticks_run, launches
@@ -349,6 +354,14 @@ class RunResult(_LazyStats):
             self.counters[name] = records[name]
         self._stats_dev = stats_dev
         self._trace_dev, self._trace_shape, self._trace = trace_dev, trace_shape, None
+        self.frames, self._anim_dev, self._anim = frames, anim_dev, None
+
+    @property
+    def anim(self):
+        if self._anim is None and self._anim_dev is not None:
+            self._anim = self._anim_dev.cpu().numpy().view(np.dtype(nat.ANIM_SAMPLE_FIELDS)).reshape(self._trace_shape)
+            self._anim_dev = None
+        return self._anim
 
     @property
     def trace(self):

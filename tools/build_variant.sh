@@ -7,6 +7,6 @@ name=$1; shift
 /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -std=c++17 -fPIC -shared "$@" \
     python_raytracer_amd/csrc/vrt_kernels.hip python_raytracer_amd/csrc/vrt_surface.hip \
     python_raytracer_amd/csrc/vrt_physics.hip python_raytracer_amd/csrc/vrt_physics_draws.hip \
-    python_raytracer_amd/csrc/vrt_physics_run.hip \
+    python_raytracer_amd/csrc/vrt_physics_run.hip python_raytracer_amd/csrc/vrt_physics_anim.hip \
     -o python_raytracer_amd/_vrt_${name}.so
 echo python_raytracer_amd/_vrt_${name}.so
