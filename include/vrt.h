@@ -877,6 +877,40 @@ int vrt_physics_run_anim(vrt_body* d_bodies, int32_t n_bodies, const uint8_t* d_
                          int32_t n_sprites, const vrt_anim_frame* d_frames, int32_t n_frame_rows, const int32_t* d_schedule,
                          vrt_anim_sample* d_anim_trace);
 
+/* vrt_physics_run_anim with the reference's random draws (vrt_physics_tick_draws's, made tick after tick): everything
+ * Object.update does per tick -- flags, the animation switch, the physics with every `solidity > random.random()` of
+ * data.py:537 and :539 in the reference's order -- for many ticks in one launch, the generator's state resident on the device
+ * throughout.  vrt_physics_run_anim's arguments in its order, then:
+ *   d_rng         [625] uint32, 4-byte aligned, as vrt_physics_tick_draws takes it: read when the launch starts, written back
+ *                 when it ends.  A chained launch passes the same pointer: the next launch goes on where this one stopped.
+ *   d_tick_draws  NULL, or [n_ticks] uint64, 8-byte aligned: the random.random() calls of each tick done; a chained launch
+ *                 passes the pointer advanced by the ticks done, as it does d_trace.
+ * Every draw the reference makes is made, for solidities >= 1 and <= 0 too, where the draws decide nothing and still move the
+ * generator on.  A body that is refused, asleep, invisible or not physical makes none; the animation switch makes none.
+ * VRT_S_PHYSICS_DRAWS is the launch's total.  An index word above 624: the launch ends before its first tick and leaves
+ * bodies, trace, sprites, d_rng and d_tick_draws untouched; VRT_S_PHYSICS_RNG_INVALID is 1 and VRT_S_PHYSICS_TICKS is 0 -- the
+ * one case in which a launch reports 0 ticks.  Work units: vrt_physics_run_anim's, one more per MT19937 state regenerated and
+ * one more per pass of 1024 tests that walks undecided tests.
+ * n_sprites = 0 and no d_anim_trace: the bodies move as vrt_physics_run's plus draws (an instance of the kernel without the
+ * sprite tables).  No material of fractional solidity: the bodies move as vrt_physics_run_anim's, and the generator advances
+ * by exactly the draws that decide nothing.  A chain of launches leaves every byte as one launch does: bodies, trace, per-tick
+ * draw counts, sprites and d_rng.
+ * VRT_ERR_ARG, before any HIP call: whatever vrt_physics_run_anim refuses, a NULL d_rng, a d_rng that is not 4-byte aligned, a
+ * d_tick_draws that is not 8-byte aligned.  ONE launch of ONE workgroup of 1024 threads with workgroup barriers only; a
+ * translation unit and kernels of its own: the four other physics kernels are unchanged. */
+/* The default budget of a run with draws.  A work unit costs 2.0 to 3.75 us on the MI355X when the passes draw
+ * (tools/bench_physics_run_draws.py, profiles/physics_run_draws_bench.json: `fluid`, whose passes regenerate four or five
+ * MT19937 states each, is the dearest); 25 ms -- 50 ms with a factor of two to spare, as for VRT_PHYSICS_RUN_BUDGET -- are 6658
+ * units at the dearest, rounded down to a power of two: a launch lasts about 15 ms at the most, plus the rest of the tick in
+ * which the budget ran out. */
+#define VRT_PHYSICS_RUN_DRAWS_BUDGET 4096
+int vrt_physics_run_draws(vrt_body* d_bodies, int32_t n_bodies, const uint8_t* d_models, int64_t models_bytes,
+                          const uint8_t* d_remap, int32_t remap_bytes, const double* d_matphys, int32_t n_materials,
+                          const vrt_physics_params* params, const vrt_physics_run_params* run, vrt_body_sample* d_trace,
+                          uint64_t* d_stats, void* stream, const int32_t* d_body_sprite, vrt_anim_sprite* d_sprites,
+                          int32_t n_sprites, const vrt_anim_frame* d_frames, int32_t n_frame_rows, const int32_t* d_schedule,
+                          vrt_anim_sample* d_anim_trace, uint32_t* d_rng, uint64_t* d_tick_draws);
+
 /* Window.chunk_update's selection loop (init.py:447-452) on the device: which world chunks the camera renders this
  * frame and at which LOD.  The voxel blocks stay resident at full resolution; a chunk's LOD is only the resolution
  * byte of its table entry (a Frame of resolution r holds the voxels at coordinates divisible by r, which is what the

@@ -28,7 +28,9 @@ PHYSICS_DRAWS_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_draws.hip")]
 PHYSICS_RUN_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_run.hip")]
 # ... and that run with the sprites animated (vrt_physics_run_anim) a sixth, again with a kernel of its own
 PHYSICS_ANIM_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_anim.hip")]
-SOURCES = UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + PHYSICS_RUN_UNITS + PHYSICS_ANIM_UNITS + \
+# ... and the animated run that makes the reference's random draws (vrt_physics_run_draws) a seventh, with kernels of its own
+PHYSICS_RUN_DRAWS_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_run_draws.hip")]
+SOURCES = UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + PHYSICS_RUN_UNITS + PHYSICS_ANIM_UNITS + PHYSICS_RUN_DRAWS_UNITS + \
     [os.path.join(HERE, "csrc", f) for f in ("vrt_math.h", "vrt_math_consts.h", "vrt_physics_common.h")]
 SOURCES.append(os.path.join(ROOT, "include", "vrt.h"))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -68,7 +70,8 @@ def build(force=False, verbose=False):
     """Compile python_raytracer_amd/_vrt.so for gfx950 (hipcc cross-compiles without a GPU)."""
     if not force and not needs_build():
         return SO_PATH
-    cmd = [HIPCC] + HIPCC_FLAGS + UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + PHYSICS_RUN_UNITS + PHYSICS_ANIM_UNITS + ["-o", SO_PATH]
+    cmd = [HIPCC] + HIPCC_FLAGS + UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + PHYSICS_RUN_UNITS + PHYSICS_ANIM_UNITS + \
+        PHYSICS_RUN_DRAWS_UNITS + ["-o", SO_PATH]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -226,6 +229,7 @@ S_PHYSICS_WORK, S_PHYSICS_TICKS = 5, 6
 BODY_EVER_MOVED, BODY_EVER_FLIPPED = 1, 2   # vrt_body.pad[0] after vrt_physics_run
 BODY_EVER_SWITCHED = 4   # ... after vrt_physics_run_anim: some tick's anim_update changed the frame at this body's turn
 PHYSICS_RUN_BUDGET = 1 << 13   # VRT_PHYSICS_RUN_BUDGET: about 23 ms of the dearest measured work units
+PHYSICS_RUN_DRAWS_BUDGET = 1 << 12   # VRT_PHYSICS_RUN_DRAWS_BUDGET: about 15 ms of the dearest measured units with draws (section 6h)
 
 
 
@@ -361,6 +365,8 @@ def lib():
                                   vp, vp, vp]
     L.vrt_physics_run_anim.restype = C.c_int
     L.vrt_physics_run_anim.argtypes = L.vrt_physics_run.argtypes + [vp, vp, i32, vp, i32, vp, vp]
+    L.vrt_physics_run_draws.restype = C.c_int
+    L.vrt_physics_run_draws.argtypes = L.vrt_physics_run_anim.argtypes + [vp, vp]
     L.vrt_canvas_blit.restype = C.c_int
     L.vrt_canvas_blit.argtypes = [vp, vp, i32, i32, vp, i64, vp]
     L.vrt_profile_begin.restype = C.c_int
@@ -396,7 +402,7 @@ EXPORTS = ["vrt_abi_version", "vrt_status_string", "vrt_last_hip_error", "vrt_de
            "vrt_trace_workspace_bytes", "vrt_trace_rays", "vrt_rng_draws",
            "vrt_synth_volume", "vrt_profile_begin", "vrt_profile_begin_kinds", "vrt_profile_end", "vrt_select_chunks", "vrt_voxelize",
            "vrt_hit_owners", "vrt_hit_surfaces", "vrt_edit_models", "vrt_stamp_model", "vrt_physics_tick",
-           "vrt_physics_tick_draws", "vrt_physics_run", "vrt_physics_run_anim"]
+           "vrt_physics_tick_draws", "vrt_physics_run", "vrt_physics_run_draws", "vrt_physics_run_anim"]
 
 
 PLAN_FIELDS = ("launches", "pool", "wt_on", "trav_words", "bm_window", "ct_cells", "n_materials", "dyn_bytes", "static_bytes")

@@ -342,10 +342,13 @@ class RunResult(_LazyStats):
     With clock= (the sprites animated): pad[0] of a record also says whether some tick's anim_update changed the frame at that
     body's turn (4); `frames`: {Sprite: its frame after the run} for every animated sprite (None without clock); `anim`: None,
     or with trace=True a numpy structured array [ticks][n] of _native.ANIM_SAMPLE_FIELDS -- every body's weight after every
-    tick, its sprite's frame (-1: not animated) and whether the body made the switch at that tick."""
+    tick, its sprite's frame (-1: not animated) and whether the body made the switch at that tick.
+    With rng= (the reference's random draws made on the device): `draws`: the random.random() calls of the run, an int (None
+    without rng); `draws_per_tick`: a numpy uint64 array [ticks_run], each tick's (None without rng); word 15 of `stats` is
+    the total as well."""
 
     def __init__(self, records, moved, stats_dev, ticks_run, launches, trace_dev, trace_shape, kernel_ms=None, frames=None,
-                 anim_dev=None):
+                 anim_dev=None, draws_per_tick=None):
         from .world import PHYSICS_COUNTER_FIELDS
         self.records, self.moved, self.kernel_ms = records, moved, kernel_ms
         self.ticks_run, self.launches = ticks_run, launches
@@ -355,6 +358,8 @@ class RunResult(_LazyStats):
         self._stats_dev = stats_dev
         self._trace_dev, self._trace_shape, self._trace = trace_dev, trace_shape, None
         self.frames, self._anim_dev, self._anim = frames, anim_dev, None
+        self.draws_per_tick = draws_per_tick
+        self.draws = int(draws_per_tick.sum()) if draws_per_tick is not None else None
 
     @property
     def anim(self):
