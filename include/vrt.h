@@ -596,6 +596,72 @@ int vrt_hit_owners(const vrt_scene* scene, const vrt_hit* d_hits, int64_t n_hits
                    const vrt_object* d_objects, int32_t n_objects, const uint8_t* d_models, const uint8_t* d_remap,
                    vrt_owner* d_owners, uint64_t* d_stats, void* stream);
 
+/* ---- per-chunk object lists ----------------------------------------------------------------------------
+ * vrt_voxelize asks every object about every voxel of every chunk it rebuilds, and vrt_hit_owners walks every object for every
+ * record.  The reference keeps, per chunk, the objects that have it (Window.chunks_objects, init.py:398-444) and merges only
+ * those.  These lists are that structure on the device, and the two passes below read them instead of the whole array.
+ *
+ * The list of chunk c holds every object k of d_objects whose box [mins, maxs) -- half-open on all axes -- meets the chunk's box
+ * [origin + c * chunk_size, origin + (c + 1) * chunk_size), in ASCENDING k, and nothing else.  Ascending k is the merge order:
+ * the voxelisation walks a list forwards (the later object wins), the owner pass backwards.  An object with an empty box
+ * (mins >= maxs on some axis) is in no list; a box that leaves the chunk box is listed only where it lies inside.  The lists
+ * are a SUPERSET of the reference's dict, which names only chunks in which the object has a voxel: whether a model holds
+ * anything there is still asked per voxel.
+ * Why the list-driven passes give the scans' results: an object can only supply a voxel c with mins <= c < maxs; such a box
+ * meets the chunk that contains c, so the object is in that chunk's list, and the list keeps the array's relative order. */
+typedef struct vrt_chunk_lists {
+    int64_t origin[3]; int32_t dims[3]; int32_t chunk_size;   /* the world chunk box the lists index: what vrt_voxelize takes */
+    int64_t n_items_cap;       /* capacity of d_items in items, < 2^31 */
+    uint32_t* d_offsets;       /* [n_chunks + 1], chunk index (cx * dims.y + cy) * dims.z + cz as in vrt_voxelize; 4-byte aligned */
+    int32_t*  d_items;         /* object indices; the list of chunk c is d_items[d_offsets[c] .. d_offsets[c + 1]) */
+} vrt_chunk_lists;
+/* The words vrt_chunk_lists_build writes into d_stats (every other word 0). */
+enum { VRT_S_LISTS_ITEMS = 8,     /* items the lists need: the sum of the list lengths, whether they fit or not */
+       VRT_S_LISTS_OVERFLOW = 9   /* 1: that is more than n_items_cap; no item was written and the sentinel is set (below) */ };
+
+/* Fills lists->d_offsets and lists->d_items for the n_objects records of d_objects (a DEVICE array, 16-byte aligned).
+ *   d_stats   [VRT_NSTATS] uint64, zeroed by the callee: the VRT_S_LISTS_* words.
+ * Deterministic: the same input gives the same bytes.  One wave per chunk takes the objects 64 at a time; a ballot marks the
+ * boxes that meet the chunk and the population count below a lane is its slot, so the order needs neither atomics nor a sort.
+ * The pass runs once to count, one workgroup sums the counts in place into d_offsets, and the pass runs again to fill: three
+ * launches, n_chunks * ceil(n_objects / 64) wave iterations per pass.
+ * OVERFLOW is never a wrong answer.  If the lists need more than n_items_cap items, VRT_S_LISTS_ITEMS says how many,
+ * VRT_S_LISTS_OVERFLOW is 1, d_items is left alone and d_offsets[n_chunks] holds the sentinel 0xFFFFFFFF.  The two consumers
+ * recognise the sentinel and walk the whole range 0 .. n_objects for every chunk: the scans' work, the scans' results.
+ * MEMORY SAFETY of the consumers.  A consumer clamps every offset it reads to n_items_cap, treats an inverted pair as an
+ * empty list and skips an item outside [0, n_objects), so lists that were built for another object array cannot make it read
+ * outside its arguments.  What it then computes is the scan over the listed objects that exist: for lists built for a LONGER
+ * array whose first n_objects records are the ones given, exactly the scan's result over those n_objects records.
+ * VRT_ERR_ARG, before any HIP call: NULL lists, d_offsets or d_stats; a chunk_size that is no power of two in 8..256; dims < 1
+ * or 2^24 - 2 chunks and more; an origin that is no multiple of chunk_size or a box outside +-2^30; n_items_cap < 0 or >= 2^31;
+ * NULL d_items with n_items_cap > 0; n_objects < 0; NULL or misaligned d_objects with n_objects > 0.  Nothing is allocated or
+ * synchronised: the call can sit on a stream next to vrt_voxelize and be captured into a hipGraph.  (A translation unit of its
+ * own: a launch failure returns VRT_ERR_HIP without updating vrt_last_hip_error().) */
+int vrt_chunk_lists_build(const vrt_object* d_objects, int32_t n_objects, const vrt_chunk_lists* lists,
+                          uint64_t* d_stats, void* stream);
+
+/* vrt_voxelize with the object loop of a chunk over that chunk's list only: d_voxels and d_world_table are byte for byte
+ * vrt_voxelize's, for the whole box and for a d_chunk_list.  One workgroup per chunk; the list's records are staged in LDS,
+ * 128 at a time; a chunk with an empty list is zeroed without touching an object.  `lists` are those of the LAST
+ * vrt_chunk_lists_build over these d_objects; their origin, dims and chunk_size must equal the call's, else VRT_ERR_ARG.
+ * Besides vrt_voxelize's own refusals and the lists' (above): d_objects and d_voxels must be 16-byte aligned.  A chunk index
+ * of d_chunk_list outside the box is skipped.  Nothing is allocated or synchronised. */
+int vrt_voxelize_lists(const vrt_object* d_objects, int32_t n_objects, const uint8_t* d_models, const uint8_t* d_remap,
+                       const int64_t* origin, const int32_t* dims, int32_t chunk_size, const uint32_t* d_chunk_list,
+                       int64_t n_list, uint32_t* d_world_table, uint8_t* d_voxels, const vrt_chunk_lists* lists, void* stream);
+
+/* vrt_hit_owners with the walk over the objects replaced by a walk over ONE list: d_owners and the four VRT_S_OWNER_* words
+ * are byte for byte vrt_hit_owners'.  The candidate rule is unchanged.  A candidate that counts yields the voxel c; the pass
+ * searches the list of the chunk OF THE LISTS' OWN BOX that contains c, from its last item to its first.  The scene's box may
+ * differ from the lists' box: if c lies outside the lists' box no listed object can hold it and the record is an orphan, as
+ * it is for vrt_hit_owners with a foreign scene.  Later candidates of an ambiguous record use their own chunk's list.  One
+ * lane per record; each lane walks on its own.
+ * Besides vrt_hit_owners' own refusals: the lists' (above).  Nothing is allocated or synchronised, so a call may be captured
+ * into a hipGraph. */
+int vrt_hit_owners_lists(const vrt_scene* scene, const vrt_hit* d_hits, int64_t n_hits,
+                         const vrt_object* d_objects, int32_t n_objects, const uint8_t* d_models, const uint8_t* d_remap,
+                         vrt_owner* d_owners, const vrt_chunk_lists* lists, uint64_t* d_stats, void* stream);
+
 /* ---- surfaces of hit records ---------------------------------------------------------------------------
  * HOW THE SURFACE LIES at a hit: the ray's velocity after the reference's reflection, the position one step on, what the
  * three neighbour lookups of that reflection asked and found, and a geometric normal -- what mirror, portal and

@@ -13,8 +13,8 @@ from .scene import PackedScene
 from .camera import Camera, RenderResult, HitResult, CastResult, ShadeResult, PathResult, SurfaceResult, release_caches
 from .canvas import Canvas
 from . import world
-from .world import OwnerResult
+from .world import OwnerResult, ChunkLists
 from .results import PhysicsResult, RunResult
 
-__all__ = ["Camera", "RenderResult", "HitResult", "CastResult", "ShadeResult", "PathResult", "SurfaceResult", "release_caches", "Canvas", "world", "OwnerResult", "PhysicsResult", "RunResult", "Material", "Frame", "PackedScene", "data", "lib", "vec2", "vec3", "quaternion", "rgb",
+__all__ = ["Camera", "RenderResult", "HitResult", "CastResult", "ShadeResult", "PathResult", "SurfaceResult", "release_caches", "Canvas", "world", "OwnerResult", "ChunkLists", "PhysicsResult", "RunResult", "Material", "Frame", "PackedScene", "data", "lib", "vec2", "vec3", "quaternion", "rgb",
            "store", "material", "material_background", "make_settings", "load_settings", "pixel_partition"]

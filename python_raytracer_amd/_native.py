@@ -30,7 +30,10 @@ PHYSICS_RUN_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_run.hip")]
 PHYSICS_ANIM_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_anim.hip")]
 # ... and the animated run that makes the reference's random draws (vrt_physics_run_draws) a seventh, with kernels of its own
 PHYSICS_RUN_DRAWS_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_run_draws.hip")]
-SOURCES = UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + PHYSICS_RUN_UNITS + PHYSICS_ANIM_UNITS + PHYSICS_RUN_DRAWS_UNITS + \
+# the per-chunk object lists and the two passes that read them (vrt_chunk_lists_build, vrt_voxelize_lists, vrt_hit_owners_lists): an
+# eighth, which restates the few helpers of vrt_kernels.hip it needs
+CHUNK_LISTS_UNITS = [os.path.join(HERE, "csrc", "vrt_chunk_lists.hip")]
+SOURCES = UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + PHYSICS_RUN_UNITS + PHYSICS_ANIM_UNITS + PHYSICS_RUN_DRAWS_UNITS + CHUNK_LISTS_UNITS + \
     [os.path.join(HERE, "csrc", f) for f in ("vrt_math.h", "vrt_math_consts.h", "vrt_physics_common.h")]
 SOURCES.append(os.path.join(ROOT, "include", "vrt.h"))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -52,6 +55,9 @@ S_RAYGEN_GROUPS = 15
 S_CAST_REJECTED = 9   # vrt_cast_rays only: rays the device refused (VRT_S_CAST_REJECTED)
 # vrt_hit_owners only (VRT_S_OWNER_*): records examined, resolved to an object, orphans, explained by two chunks
 S_OWNER_EXAMINED, S_OWNER_RESOLVED, S_OWNER_ORPHANS, S_OWNER_AMBIGUOUS = 8, 4, 9, 10
+# vrt_chunk_lists_build only (VRT_S_LISTS_*): items the lists need, 1 if that is more than their capacity
+S_LISTS_ITEMS, S_LISTS_OVERFLOW = 8, 9
+LISTS_SENTINEL = 0xFFFFFFFF   # d_offsets[n_chunks] of lists that did not fit: the consumers walk every object
 # vrt_hit_surfaces only (VRT_S_SURFACE_*): records examined, resolved, orphans, explained differently by two chunks, refused
 # by the device, resolved with no open incoming side
 S_SURFACE_EXAMINED, S_SURFACE_RESOLVED, S_SURFACE_ORPHANS, S_SURFACE_AMBIGUOUS, S_SURFACE_INVALID, S_SURFACE_ENCLOSED = 8, 4, 9, 10, 11, 12
@@ -71,7 +77,7 @@ def build(force=False, verbose=False):
     if not force and not needs_build():
         return SO_PATH
     cmd = [HIPCC] + HIPCC_FLAGS + UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + PHYSICS_RUN_UNITS + PHYSICS_ANIM_UNITS + \
-        PHYSICS_RUN_DRAWS_UNITS + ["-o", SO_PATH]
+        PHYSICS_RUN_DRAWS_UNITS + CHUNK_LISTS_UNITS + ["-o", SO_PATH]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -144,6 +150,12 @@ class VrtOwner(C.Structure):
 OWNER_FIELDS = [("object", "<i4"), ("resolution", "<i4"), ("voxel", "<i4", 3), ("local", "<i4", 3)]
 OWNER_BYTES = 32
 OWNER_NONE, OWNER_ORPHAN = -1, -2   # vrt_owner.object of a record that is no hit / that no object accounts for
+
+
+class VrtChunkLists(C.Structure):
+    """vrt_chunk_lists (include/vrt.h): the chunk box, the capacity of d_items and the two device arrays, 64 bytes."""
+    _fields_ = [("origin", C.c_int64 * 3), ("dims", C.c_int32 * 3), ("chunk_size", C.c_int32), ("n_items_cap", C.c_int64),
+                ("d_offsets", C.c_void_p), ("d_items", C.c_void_p)]
 
 
 class VrtSurface(C.Structure):
@@ -350,6 +362,12 @@ def lib():
     L.vrt_voxelize.argtypes = [vp, i32, vp, vp, C.POINTER(i64), C.POINTER(i32), i32, vp, i64, vp, vp, vp]
     L.vrt_hit_owners.restype = C.c_int
     L.vrt_hit_owners.argtypes = [C.POINTER(VrtScene), vp, i64, vp, i32, vp, vp, vp, vp, vp]
+    L.vrt_chunk_lists_build.restype = C.c_int
+    L.vrt_chunk_lists_build.argtypes = [vp, i32, C.POINTER(VrtChunkLists), vp, vp]
+    L.vrt_voxelize_lists.restype = C.c_int
+    L.vrt_voxelize_lists.argtypes = L.vrt_voxelize.argtypes[:-1] + [C.POINTER(VrtChunkLists), vp]
+    L.vrt_hit_owners_lists.restype = C.c_int
+    L.vrt_hit_owners_lists.argtypes = [C.POINTER(VrtScene), vp, i64, vp, i32, vp, vp, vp, C.POINTER(VrtChunkLists), vp, vp]
     L.vrt_hit_surfaces.restype = C.c_int
     L.vrt_hit_surfaces.argtypes = [C.POINTER(VrtScene), vp, vp, i64, vp, vp, vp]
     L.vrt_edit_models.restype = C.c_int
@@ -401,7 +419,7 @@ EXPORTS = ["vrt_abi_version", "vrt_status_string", "vrt_last_hip_error", "vrt_de
            "vrt_pow_memo_create", "vrt_occupancy_build", "vrt_canvas_blit", "vrt_world_tables_bytes", "vrt_world_tables_build",
            "vrt_trace_workspace_bytes", "vrt_trace_rays", "vrt_rng_draws",
            "vrt_synth_volume", "vrt_profile_begin", "vrt_profile_begin_kinds", "vrt_profile_end", "vrt_select_chunks", "vrt_voxelize",
-           "vrt_hit_owners", "vrt_hit_surfaces", "vrt_edit_models", "vrt_stamp_model", "vrt_physics_tick",
+           "vrt_hit_owners", "vrt_chunk_lists_build", "vrt_voxelize_lists", "vrt_hit_owners_lists", "vrt_hit_surfaces", "vrt_edit_models", "vrt_stamp_model", "vrt_physics_tick",
            "vrt_physics_tick_draws", "vrt_physics_run", "vrt_physics_run_draws", "vrt_physics_run_anim"]
 
 
