@@ -977,6 +977,39 @@ int vrt_physics_run_draws(vrt_body* d_bodies, int32_t n_bodies, const uint8_t* d
                           int32_t n_sprites, const vrt_anim_frame* d_frames, int32_t n_frame_rows, const int32_t* d_schedule,
                           vrt_anim_sample* d_anim_trace, uint32_t* d_rng, uint64_t* d_tick_draws);
 
+/* Many runs in one launch: n_runs what-if copies of one world's bodies -- the same models, other positions and velocities --
+ * each stepped as vrt_physics_run steps its own, bit for bit: the camera from the followed body, the flags and the validation at
+ * the start of every tick, the body walk, the ordered compaction and the serial sums, the step cap, the pad[0] bits.  A run is a
+ * sequential chain and takes one workgroup; runs are independent, so the call is ONE launch of n_runs workgroups of 1024 threads
+ * that never communicate: no grid barrier, no cooperative launch, no atomics on memory another workgroup reads, nothing that
+ * waits on memory.  d_models, d_remap and d_matphys are read-only and shared by all runs.
+ *   d_bodies      [n_runs][n_bodies] in, out: run r's records as vrt_physics_run takes them.
+ *   run           shared by all runs: camera, offset, follow (an index into each run's own bodies), distances, budget -- and
+ *                 n_ticks, here the TOTAL of the run, not what is left of it.
+ *   d_ticks_done  [n_runs] int32, 4-byte aligned, in, out: the ticks run r has behind it; 0 before the first launch.
+ *   d_trace       NULL, or [n_runs][run->n_ticks][n_bodies] vrt_body_sample, 8-byte aligned, indexed by ABSOLUTE tick:
+ *                 d_trace[(r * n_ticks + tick) * n_bodies + k] is body k of run r after tick `tick`.
+ *   d_stats       [n_runs][VRT_NSTATS] uint64, zeroed by the callee: vrt_physics_run's words for run r's share of this launch.
+ * Each workgroup counts work as vrt_physics_run does and stops at the first tick boundary at or past run->budget, or when its
+ * run has n_ticks behind it; before it returns it adds the ticks it did (VRT_S_PHYSICS_TICKS, at least one) to d_ticks_done[r].
+ * The caller launches again with the SAME pointers while any d_ticks_done[r] < n_ticks: a run that is already done writes zeroed
+ * statistics (TICKS = 0) and touches neither its bodies nor its trace.  Chained launches leave every byte of the bodies and of
+ * the trace as one launch does, and the per-run statistics add up.  Every launch ends in bounded time on any input.
+ * An entry of d_ticks_done outside [0, n_ticks] is device data: the kernel treats that run as done, touches nothing of it and
+ * sets VRT_S_PHYSICS_BATCH_BADTICK in its statistics; the other runs are not affected.
+ * It makes no random draws and animates nothing: a material of fractional solidity is not solid, as for vrt_physics_run
+ * (batches with draws or a clock would need a generator and sprite tables per run).
+ * n_bodies = 0: nothing to do, every run reports n_ticks done (TICKS = what was left).  VRT_ERR_ARG, before any HIP call:
+ * whatever vrt_physics_run refuses, n_runs outside [1, VRT_PHYSICS_BATCH_MAX_RUNS], n_runs * n_bodies > 2^20, NULL or
+ * misaligned (4 bytes) d_ticks_done, NULL d_stats, misaligned (8 bytes) d_trace.  Nothing is allocated or synchronised.  A kernel
+ * and a translation unit of its own: the other physics kernels are unchanged. */
+#define VRT_PHYSICS_BATCH_MAX_RUNS 4096
+enum { VRT_S_PHYSICS_BATCH_BADTICK = 4 /* 1 if d_ticks_done[r] was outside [0, n_ticks]: the run was left alone (vrt_physics_run_batch only) */ };
+int vrt_physics_run_batch(vrt_body* d_bodies, int32_t n_runs, int32_t n_bodies, const uint8_t* d_models, int64_t models_bytes,
+                          const uint8_t* d_remap, int32_t remap_bytes, const double* d_matphys, int32_t n_materials,
+                          const vrt_physics_params* params, const vrt_physics_run_params* run, int32_t* d_ticks_done,
+                          vrt_body_sample* d_trace, uint64_t* d_stats, void* stream);
+
 /* Window.chunk_update's selection loop (init.py:447-452) on the device: which world chunks the camera renders this
  * frame and at which LOD.  The voxel blocks stay resident at full resolution; a chunk's LOD is only the resolution
  * byte of its table entry (a Frame of resolution r holds the voxels at coordinates divisible by r, which is what the

@@ -14,7 +14,7 @@ from .camera import Camera, RenderResult, HitResult, CastResult, ShadeResult, Pa
 from .canvas import Canvas
 from . import world
 from .world import OwnerResult, ChunkLists
-from .results import PhysicsResult, RunResult
+from .results import BatchRunResult, PhysicsResult, RunResult
 
-__all__ = ["Camera", "RenderResult", "HitResult", "CastResult", "ShadeResult", "PathResult", "SurfaceResult", "release_caches", "Canvas", "world", "OwnerResult", "ChunkLists", "PhysicsResult", "RunResult", "Material", "Frame", "PackedScene", "data", "lib", "vec2", "vec3", "quaternion", "rgb",
+__all__ = ["Camera", "RenderResult", "HitResult", "CastResult", "ShadeResult", "PathResult", "SurfaceResult", "release_caches", "Canvas", "world", "OwnerResult", "ChunkLists", "PhysicsResult", "RunResult", "BatchRunResult", "Material", "Frame", "PackedScene", "data", "lib", "vec2", "vec3", "quaternion", "rgb",
            "store", "material", "material_background", "make_settings", "load_settings", "pixel_partition"]

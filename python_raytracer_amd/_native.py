@@ -33,7 +33,10 @@ PHYSICS_RUN_DRAWS_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_run_draws.hip
 # the per-chunk object lists and the two passes that read them (vrt_chunk_lists_build, vrt_voxelize_lists, vrt_hit_owners_lists): an
 # eighth, which restates the few helpers of vrt_kernels.hip it needs
 CHUNK_LISTS_UNITS = [os.path.join(HERE, "csrc", "vrt_chunk_lists.hip")]
+# many what-if runs in one launch, one workgroup each (vrt_physics_run_batch): a ninth, again with a kernel of its own
+PHYSICS_BATCH_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_batch.hip")]
 SOURCES = UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + PHYSICS_RUN_UNITS + PHYSICS_ANIM_UNITS + PHYSICS_RUN_DRAWS_UNITS + CHUNK_LISTS_UNITS + \
+    PHYSICS_BATCH_UNITS + \
     [os.path.join(HERE, "csrc", f) for f in ("vrt_math.h", "vrt_math_consts.h", "vrt_physics_common.h")]
 SOURCES.append(os.path.join(ROOT, "include", "vrt.h"))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -77,7 +80,7 @@ def build(force=False, verbose=False):
     if not force and not needs_build():
         return SO_PATH
     cmd = [HIPCC] + HIPCC_FLAGS + UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + PHYSICS_RUN_UNITS + PHYSICS_ANIM_UNITS + \
-        PHYSICS_RUN_DRAWS_UNITS + CHUNK_LISTS_UNITS + ["-o", SO_PATH]
+        PHYSICS_RUN_DRAWS_UNITS + CHUNK_LISTS_UNITS + PHYSICS_BATCH_UNITS + ["-o", SO_PATH]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -242,6 +245,8 @@ BODY_EVER_MOVED, BODY_EVER_FLIPPED = 1, 2   # vrt_body.pad[0] after vrt_physics_
 BODY_EVER_SWITCHED = 4   # ... after vrt_physics_run_anim: some tick's anim_update changed the frame at this body's turn
 PHYSICS_RUN_BUDGET = 1 << 13   # VRT_PHYSICS_RUN_BUDGET: about 23 ms of the dearest measured work units
 PHYSICS_RUN_DRAWS_BUDGET = 1 << 12   # VRT_PHYSICS_RUN_DRAWS_BUDGET: about 15 ms of the dearest measured units with draws (section 6h)
+# vrt_physics_run_batch only: runs per launch at most, and the word a run sets whose d_ticks_done entry was out of range
+PHYSICS_BATCH_MAX_RUNS, S_PHYSICS_BATCH_BADTICK = 4096, 4
 
 
 
@@ -385,6 +390,9 @@ def lib():
     L.vrt_physics_run_anim.argtypes = L.vrt_physics_run.argtypes + [vp, vp, i32, vp, i32, vp, vp]
     L.vrt_physics_run_draws.restype = C.c_int
     L.vrt_physics_run_draws.argtypes = L.vrt_physics_run_anim.argtypes + [vp, vp]
+    L.vrt_physics_run_batch.restype = C.c_int
+    L.vrt_physics_run_batch.argtypes = [vp, i32, i32, vp, i64, vp, i32, vp, i32, C.POINTER(VrtPhysicsParams), C.POINTER(VrtPhysicsRunParams),
+                                        vp, vp, vp, vp]
     L.vrt_canvas_blit.restype = C.c_int
     L.vrt_canvas_blit.argtypes = [vp, vp, i32, i32, vp, i64, vp]
     L.vrt_profile_begin.restype = C.c_int
@@ -420,7 +428,7 @@ EXPORTS = ["vrt_abi_version", "vrt_status_string", "vrt_last_hip_error", "vrt_de
            "vrt_trace_workspace_bytes", "vrt_trace_rays", "vrt_rng_draws",
            "vrt_synth_volume", "vrt_profile_begin", "vrt_profile_begin_kinds", "vrt_profile_end", "vrt_select_chunks", "vrt_voxelize",
            "vrt_hit_owners", "vrt_chunk_lists_build", "vrt_voxelize_lists", "vrt_hit_owners_lists", "vrt_hit_surfaces", "vrt_edit_models", "vrt_stamp_model", "vrt_physics_tick",
-           "vrt_physics_tick_draws", "vrt_physics_run", "vrt_physics_run_draws", "vrt_physics_run_anim"]
+           "vrt_physics_tick_draws", "vrt_physics_run", "vrt_physics_run_batch", "vrt_physics_run_draws", "vrt_physics_run_anim"]
 
 
 PLAN_FIELDS = ("launches", "pool", "wt_on", "trav_words", "bm_window", "ct_cells", "n_materials", "dyn_bytes", "static_bytes")

@@ -374,3 +374,55 @@ class RunResult(_LazyStats):
             self._trace = self._trace_dev.cpu().numpy().view(np.dtype(nat.BODY_SAMPLE_FIELDS)).reshape(self._trace_shape)
             self._trace_dev = None
         return self._trace
+
+
+class BatchRunResult(_LazyStats):
+    """What DeviceWorld.run_many() did: K variants of one world, each stepped as run() steps a twin, none written into the
+    caller's objects.  `records`: [K][n] vrt_body (include/vrt.h) after the last tick, as RunResult.records per variant, pad[0]
+    included; `counters`: their `out` fields, [K][n].  `ticks_run`: [K] ticks each variant has behind it, always the ticks asked
+    for; `launches`: the device launches the batch took (more than one where the work budget ended some run's share early).
+    `kernel_ms`: the launches' summed time if it was asked for.
+    `stats`: numpy int64[K][16], copied from the device on first use, summed over the launches: RunResult's words per variant
+    (8 = body turns stepped, 9 = refusals, 10 = steps, 11 = blocked steps, 12 = contacts, 13 = transfers, 14 = capped step
+    loops, 5 = work units, 6 = ticks done).
+    `trace`: None, or with trace=True a numpy structured array [K][ticks][n] of _native.BODY_SAMPLE_FIELDS, copied from the
+    device on first use.
+    final(k): where variant k ends.  apply(k, objects): commit variant k to the objects."""
+
+    def __init__(self, records, start, changes, stats_dev, ticks_run, launches, trace_dev, trace_shape, kernel_ms=None):
+        from .world import PHYSICS_COUNTER_FIELDS
+        self.records, self.kernel_ms = records, kernel_ms
+        self.ticks_run, self.launches = ticks_run, launches
+        self.counters = np.zeros(records.shape, np.dtype(PHYSICS_COUNTER_FIELDS))
+        for name, *_ in PHYSICS_COUNTER_FIELDS:
+            self.counters[name] = records[name]
+        self._start, self._changes = start, changes
+        self._stats_dev = stats_dev
+        self._trace_dev, self._trace_shape, self._trace = trace_dev, trace_shape, None
+
+    @property
+    def trace(self):
+        if self._trace is None and self._trace_dev is not None:
+            self._trace = self._trace_dev.cpu().numpy().view(np.dtype(nat.BODY_SAMPLE_FIELDS)).reshape(self._trace_shape)
+            self._trace_dev = None
+        return self._trace
+
+    def final(self, k):
+        """(pos [n][3], vel [n][3]) of variant k after its last tick, float64 copies."""
+        return self.records[k]["pos"].copy(), self.records[k]["vel"].copy()
+
+    def apply(self, k, objects):
+        """Write variant k's outcome into `objects` -- the objects run_many() was given, unchanged since -- exactly as run()
+        writes its own into a twin that had the variant applied: first the variant itself (Object.move, the velocity), then
+        pos, vel, mins, maxs, visible, cam_pos and redraw from the records.  Returns the Objects whose position changed
+        during the run, in physics order (RunResult.moved).  update(objects) follows, as after run()."""
+        from .world import _write_back_run
+        objects = list(objects)
+        if len(objects) != self.records.shape[1]:
+            raise ValueError("apply(): %d objects for records of %d" % (len(objects), self.records.shape[1]))
+        for at, pos, vel in self._changes[k]:
+            if pos is not None:
+                objects[at].move(pos)
+            if vel is not None:
+                objects[at].vel = type(vel)(vel.x, vel.y, vel.z)
+        return _write_back_run(objects, self.records[k], self._start[k])
