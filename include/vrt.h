@@ -998,7 +998,7 @@ int vrt_physics_run_draws(vrt_body* d_bodies, int32_t n_bodies, const uint8_t* d
  * An entry of d_ticks_done outside [0, n_ticks] is device data: the kernel treats that run as done, touches nothing of it and
  * sets VRT_S_PHYSICS_BATCH_BADTICK in its statistics; the other runs are not affected.
  * It makes no random draws and animates nothing: a material of fractional solidity is not solid, as for vrt_physics_run
- * (batches with draws or a clock would need a generator and sprite tables per run).
+ * (vrt_physics_run_batch_draws, below, is the batch with draws; a batch with a clock would need sprite tables per run).
  * n_bodies = 0: nothing to do, every run reports n_ticks done (TICKS = what was left).  VRT_ERR_ARG, before any HIP call:
  * whatever vrt_physics_run refuses, n_runs outside [1, VRT_PHYSICS_BATCH_MAX_RUNS], n_runs * n_bodies > 2^20, NULL or
  * misaligned (4 bytes) d_ticks_done, NULL d_stats, misaligned (8 bytes) d_trace.  Nothing is allocated or synchronised.  A kernel
@@ -1009,6 +1009,44 @@ int vrt_physics_run_batch(vrt_body* d_bodies, int32_t n_runs, int32_t n_bodies, 
                           const uint8_t* d_remap, int32_t remap_bytes, const double* d_matphys, int32_t n_materials,
                           const vrt_physics_params* params, const vrt_physics_run_params* run, int32_t* d_ticks_done,
                           vrt_body_sample* d_trace, uint64_t* d_stats, void* stream);
+
+/* vrt_physics_run_batch with the reference's random draws: n_runs what-if copies of one world's bodies, each with a generator
+ * of its own, each stepped as vrt_physics_run_draws without sprite tables (n_sprites = 0, no d_anim_trace) steps its own, bit
+ * for bit -- every `solidity > random.random()` of data.py:537 and :539 made from that run's MT19937 state in the reference's
+ * order.  ONE launch of n_runs workgroups of 1024 threads that never communicate: workgroup barriers only, no grid barrier, no
+ * cooperative launch, no atomics on memory another workgroup reads, nothing that waits on memory.  vrt_physics_run_batch's
+ * arguments in its order, with its meaning (n_ticks is the TOTAL of a run, d_trace is indexed by absolute tick), then:
+ *   d_rng         [n_runs][625] uint32, 4-byte aligned: run r's generator as vrt_physics_tick_draws takes it, read when a launch
+ *                 starts on run r and written back when that launch ends its share of run r.  A chained launch passes the same
+ *                 pointer and goes on where the last one stopped.
+ *   d_tick_draws  NULL, or [n_runs][run->n_ticks] uint64, 8-byte aligned, indexed by ABSOLUTE tick: the random.random() calls of
+ *                 tick `tick` of run r.  A launch writes only the ticks it does.
+ *   d_stats       [n_runs][VRT_NSTATS] uint64, zeroed by the callee: vrt_physics_run_draws's words for run r's share of this
+ *                 launch -- VRT_S_PHYSICS_DRAWS, _WORK, _TICKS and the rest; none of them is word VRT_S_PHYSICS_BATCH_BADTICK (4)
+ *                 or VRT_S_PHYSICS_RNG_INVALID (7).
+ * Each workgroup counts the work units of vrt_physics_run_draws and stops at the first tick boundary at or past run->budget, or
+ * when its run has n_ticks behind it, and adds the ticks it did to d_ticks_done[r]; the caller launches again with the SAME
+ * pointers while any d_ticks_done[r] < n_ticks.  Chained launches leave every byte of the bodies, the trace, d_tick_draws and
+ * d_rng as one launch does, and the per-run statistics add up.  Every launch ends in bounded time on any input.  Per run:
+ *   a run that is done (d_ticks_done[r] == n_ticks) touches nothing of its own but its zeroed statistics (TICKS = 0): not its
+ *     bodies, not its trace, not its d_tick_draws, and in particular not its d_rng;
+ *   an entry of d_ticks_done outside [0, n_ticks] is vrt_physics_run_batch's case: the run is left alone -- bodies, trace,
+ *     d_rng, d_tick_draws and the entry itself -- and VRT_S_PHYSICS_BATCH_BADTICK is 1 in its statistics; it is checked before
+ *     the generator is read;
+ *   an index word (d_rng[r][624]) above 624: the run is left alone -- its bodies, trace, d_rng, d_tick_draws and
+ *     d_ticks_done[r] are untouched -- and VRT_S_PHYSICS_RNG_INVALID is 1 in its statistics (TICKS = 0).  The caller must not
+ *     launch again for such a run: it will never advance;
+ *   n_bodies == 0: every tick is done (TICKS = what was left, d_ticks_done[r] = n_ticks), the ticks left get 0 in d_tick_draws,
+ *     and d_rng is untouched.
+ * In each of these cases the other runs are not affected.
+ * VRT_ERR_ARG, before any HIP call: whatever vrt_physics_run_batch refuses, a NULL d_rng, a d_rng that is not 4-byte aligned, a
+ * d_tick_draws that is not 8-byte aligned.  Nothing is allocated or synchronised.  The default budget of a run with draws is
+ * VRT_PHYSICS_RUN_DRAWS_BUDGET.  A kernel and a translation unit of its own (vrt_physics_batch_draws.hip): the other physics
+ * kernels are unchanged. */
+int vrt_physics_run_batch_draws(vrt_body* d_bodies, int32_t n_runs, int32_t n_bodies, const uint8_t* d_models, int64_t models_bytes,
+                                const uint8_t* d_remap, int32_t remap_bytes, const double* d_matphys, int32_t n_materials,
+                                const vrt_physics_params* params, const vrt_physics_run_params* run, int32_t* d_ticks_done,
+                                vrt_body_sample* d_trace, uint64_t* d_stats, void* stream, uint32_t* d_rng, uint64_t* d_tick_draws);
 
 /* Window.chunk_update's selection loop (init.py:447-452) on the device: which world chunks the camera renders this
  * frame and at which LOD.  The voxel blocks stay resident at full resolution; a chunk's LOD is only the resolution

@@ -35,8 +35,10 @@ PHYSICS_RUN_DRAWS_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_run_draws.hip
 CHUNK_LISTS_UNITS = [os.path.join(HERE, "csrc", "vrt_chunk_lists.hip")]
 # many what-if runs in one launch, one workgroup each (vrt_physics_run_batch): a ninth, again with a kernel of its own
 PHYSICS_BATCH_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_batch.hip")]
+# ... and those runs with the reference's random draws, a generator per run (vrt_physics_run_batch_draws): a tenth, likewise
+PHYSICS_BATCH_DRAWS_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_batch_draws.hip")]
 SOURCES = UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + PHYSICS_RUN_UNITS + PHYSICS_ANIM_UNITS + PHYSICS_RUN_DRAWS_UNITS + CHUNK_LISTS_UNITS + \
-    PHYSICS_BATCH_UNITS + \
+    PHYSICS_BATCH_UNITS + PHYSICS_BATCH_DRAWS_UNITS + \
     [os.path.join(HERE, "csrc", f) for f in ("vrt_math.h", "vrt_math_consts.h", "vrt_physics_common.h")]
 SOURCES.append(os.path.join(ROOT, "include", "vrt.h"))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -80,7 +82,7 @@ def build(force=False, verbose=False):
     if not force and not needs_build():
         return SO_PATH
     cmd = [HIPCC] + HIPCC_FLAGS + UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + PHYSICS_RUN_UNITS + PHYSICS_ANIM_UNITS + \
-        PHYSICS_RUN_DRAWS_UNITS + CHUNK_LISTS_UNITS + PHYSICS_BATCH_UNITS + ["-o", SO_PATH]
+        PHYSICS_RUN_DRAWS_UNITS + CHUNK_LISTS_UNITS + PHYSICS_BATCH_UNITS + PHYSICS_BATCH_DRAWS_UNITS + ["-o", SO_PATH]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -393,6 +395,8 @@ def lib():
     L.vrt_physics_run_batch.restype = C.c_int
     L.vrt_physics_run_batch.argtypes = [vp, i32, i32, vp, i64, vp, i32, vp, i32, C.POINTER(VrtPhysicsParams), C.POINTER(VrtPhysicsRunParams),
                                         vp, vp, vp, vp]
+    L.vrt_physics_run_batch_draws.restype = C.c_int
+    L.vrt_physics_run_batch_draws.argtypes = L.vrt_physics_run_batch.argtypes + [vp, vp]
     L.vrt_canvas_blit.restype = C.c_int
     L.vrt_canvas_blit.argtypes = [vp, vp, i32, i32, vp, i64, vp]
     L.vrt_profile_begin.restype = C.c_int
@@ -428,7 +432,8 @@ EXPORTS = ["vrt_abi_version", "vrt_status_string", "vrt_last_hip_error", "vrt_de
            "vrt_trace_workspace_bytes", "vrt_trace_rays", "vrt_rng_draws",
            "vrt_synth_volume", "vrt_profile_begin", "vrt_profile_begin_kinds", "vrt_profile_end", "vrt_select_chunks", "vrt_voxelize",
            "vrt_hit_owners", "vrt_chunk_lists_build", "vrt_voxelize_lists", "vrt_hit_owners_lists", "vrt_hit_surfaces", "vrt_edit_models", "vrt_stamp_model", "vrt_physics_tick",
-           "vrt_physics_tick_draws", "vrt_physics_run", "vrt_physics_run_batch", "vrt_physics_run_draws", "vrt_physics_run_anim"]
+           "vrt_physics_tick_draws", "vrt_physics_run", "vrt_physics_run_batch", "vrt_physics_run_batch_draws",
+           "vrt_physics_run_draws", "vrt_physics_run_anim"]
 
 
 PLAN_FIELDS = ("launches", "pool", "wt_on", "trav_words", "bm_window", "ct_cells", "n_materials", "dyn_bytes", "static_bytes")

@@ -387,9 +387,14 @@ class BatchRunResult(_LazyStats):
     loops, 5 = work units, 6 = ticks done).
     `trace`: None, or with trace=True a numpy structured array [K][ticks][n] of _native.BODY_SAMPLE_FIELDS, copied from the
     device on first use.
-    final(k): where variant k ends.  apply(k, objects): commit variant k to the objects."""
+    final(k): where variant k ends.  apply(k, objects): commit variant k to the objects.
+    With rng= (the reference's random draws made on the device, a generator per variant): `draws`: numpy uint64 [K], the
+    random.random() calls of each variant (word 15 of its `stats` as well); `draws_per_tick`: numpy uint64 [K][ticks];
+    rng_state(k): the state variant k's generator ends in; apply(k, objects, rng=g) also sets g to it.  `draws` and
+    `draws_per_tick` are None for a batch without rng=, and so is what rng_state(k) returns."""
 
-    def __init__(self, records, start, changes, stats_dev, ticks_run, launches, trace_dev, trace_shape, kernel_ms=None):
+    def __init__(self, records, start, changes, stats_dev, ticks_run, launches, trace_dev, trace_shape, kernel_ms=None,
+                 draws_per_tick=None, rng_words=None, rng_start=None):
         from .world import PHYSICS_COUNTER_FIELDS
         self.records, self.kernel_ms = records, kernel_ms
         self.ticks_run, self.launches = ticks_run, launches
@@ -399,6 +404,17 @@ class BatchRunResult(_LazyStats):
         self._start, self._changes = start, changes
         self._stats_dev = stats_dev
         self._trace_dev, self._trace_shape, self._trace = trace_dev, trace_shape, None
+        self.draws_per_tick = draws_per_tick
+        self.draws = draws_per_tick.sum(axis=1, dtype=np.uint64) if draws_per_tick is not None else None
+        self._rng_words, self._rng_start = rng_words, rng_start
+
+    def rng_state(self, k):
+        """The state variant k's generator ends in, as run(rng=) would have left it: the tuple random.Random.setstate takes,
+        with the version and gauss_next of the generator variant k was handed.  None for a batch without rng=."""
+        if self._rng_words is None:
+            return None
+        version, _, gauss_next = self._rng_start[k]
+        return version, tuple(self._rng_words[k].tolist()), gauss_next
 
     @property
     def trace(self):
@@ -411,15 +427,23 @@ class BatchRunResult(_LazyStats):
         """(pos [n][3], vel [n][3]) of variant k after its last tick, float64 copies."""
         return self.records[k]["pos"].copy(), self.records[k]["vel"].copy()
 
-    def apply(self, k, objects):
+    def apply(self, k, objects, rng=None):
         """Write variant k's outcome into `objects` -- the objects run_many() was given, unchanged since -- exactly as run()
         writes its own into a twin that had the variant applied: first the variant itself (Object.move, the velocity), then
         pos, vel, mins, maxs, visible, cam_pos and redraw from the records.  Returns the Objects whose position changed
-        during the run, in physics order (RunResult.moved).  update(objects) follows, as after run()."""
+        during the run, in physics order (RunResult.moved).  update(objects) follows, as after run().
+        rng: a random.Random (anything else: TypeError); if the batch drew, it is set to rng_state(k), where run(rng=) on
+        the variant's twin would have left variant k's generator.  A batch without rng= leaves it alone."""
         from .world import _write_back_run
         objects = list(objects)
         if len(objects) != self.records.shape[1]:
             raise ValueError("apply(): %d objects for records of %d" % (len(objects), self.records.shape[1]))
+        if rng is not None:
+            import random
+            if not isinstance(rng, random.Random):
+                raise TypeError("apply(): rng must be a random.Random, not %r" % (rng,))
+            if self._rng_words is not None:
+                rng.setstate(self.rng_state(k))
         for at, pos, vel in self._changes[k]:
             if pos is not None:
                 objects[at].move(pos)
