@@ -1048,6 +1048,63 @@ int vrt_physics_run_batch_draws(vrt_body* d_bodies, int32_t n_runs, int32_t n_bo
                                 const vrt_physics_params* params, const vrt_physics_run_params* run, int32_t* d_ticks_done,
                                 vrt_body_sample* d_trace, uint64_t* d_stats, void* stream, uint32_t* d_rng, uint64_t* d_tick_draws);
 
+/* The CONTACT LOG of a batch of runs: who touched whom, where, along which direction and between which materials.  A contact is
+ * one execution of the block under `if self_mat and self_mat.solidity > random.random():` of Object.update_physics
+ * (data.py:532-542): one slab voxel at which a solid voxel of another object faces a solid voxel of the mover -- what
+ * vrt_body.contacts and VRT_S_PHYSICS_CONTACTS count.  The order of a run's log is the reference's: ticks -> bodies in physics
+ * order -> steps of the body's step loop -> met bodies in array order -> x -> y -> z.  A transfer of velocity without a contact
+ * is no event. */
+typedef struct vrt_contact {     /* 40 bytes */
+    int32_t tick;                /* absolute tick of the run, from 0 */
+    int32_t mover;               /* index of the body whose step it is */
+    int32_t other;               /* index of the body it met */
+    int32_t step;                /* iteration of the mover's step loop in this tick, from 0 */
+    int32_t voxel[3];            /* world voxel of `other` that was met; the mover's voxel is voxel - dir */
+    int8_t  dir[3];              /* vel_dir of the step */
+    uint8_t mat_other;           /* world material id of the other's voxel (a row of d_matphys) */
+    uint8_t mat_mover;           /* world material id of the mover's voxel */
+    uint8_t reserved[7];         /* 0 */
+} vrt_contact;
+enum { VRT_CONTACTS_VOXELS = 0, /* every contact */
+       VRT_CONTACTS_PAIRS = 1   /* the first record, in the order above, of every (tick, mover, step, other): one event per touch */ };
+typedef struct vrt_contact_log {
+    vrt_contact*   d_records;    /* [n_runs][capacity], 8-byte aligned; may be NULL iff capacity == 0 */
+    uint64_t*      d_counts;     /* [n_runs] in, out, 8-byte aligned */
+    const uint8_t* d_mask;       /* [n_bodies], or NULL: every contact */
+    int32_t        capacity;     /* per run, >= 0 */
+    int32_t        mode;         /* VRT_CONTACTS_VOXELS or VRT_CONTACTS_PAIRS */
+} vrt_contact_log;
+
+/* vrt_physics_run_batch with a contact log per run: vrt_physics_run_batch's arguments in its order, with its meaning, then
+ *   d_rng         NULL: the batch without draws, vrt_physics_run_batch's tick, in which fractional solidity is not solid;
+ *                 d_tick_draws is then not looked at.  Otherwise vrt_physics_run_batch_draws's tick with its d_rng and
+ *                 d_tick_draws, generator handling included: every rule stated there holds here.
+ *   log           the log, read before the call returns; its arrays are device memory that stays with the caller:
+ *     d_mask      one byte per body, shared by all runs: bit 0 = log contacts in which this body is the mover, bit 1 = in which it
+ *                 is the other; a contact is logged iff (mask[mover] & 1) || (mask[other] & 2).  Only bits 0 and 1 are read.
+ *     d_counts    run r's count: the records run r would have logged after the filters.  It is read when a launch starts on run r
+ *                 and written back when that launch ends its share, so chained launches continue the log where it stood, as
+ *                 d_ticks_done continues the ticks; it keeps counting past capacity.  0 before the first launch of a fresh log.
+ *     d_records   record p of run r goes to d_records[r * capacity + p] iff p < capacity; later ones are counted, not stored.  A
+ *                 count at or past capacity on entry stores nothing and goes on counting.
+ * ONE launch of n_runs workgroups of 1024 threads that never communicate: workgroup barriers only, no grid barrier, no atomics
+ * on memory another workgroup reads, nothing that waits on memory.  The tick is the restated entry point's statement for
+ * statement, and the work units are counted exactly as there: a run with a log stops at the same tick boundaries and reports
+ * the same statistics and d_ticks_done as the same run without one, and leaves the same bytes in its bodies, its trace, its
+ * d_tick_draws and its d_rng.  After a pass's
+ * contacts are compacted in order the logging lanes are ranked by the same ordered compaction and each writes its own record.
+ * A run that is left alone (an entry of d_ticks_done outside [0, n_ticks], an index word of its generator above 624, or
+ * already done) leaves its count and records alone; so does n_bodies == 0.
+ * VRT_ERR_ARG, before any HIP call: whatever the restated entry point refuses (of d_rng: misalignment), a NULL log, capacity < 0, a
+ * mode other than the two, NULL or misaligned (8 bytes) d_counts, d_records NULL with capacity > 0 or misaligned (8 bytes),
+ * n_runs * capacity > 2^31 - 1.  Nothing is allocated or synchronised.  Two kernels and a translation unit of their own
+ * (vrt_physics_contacts.hip): the other physics kernels are unchanged, and so is VRT_ABI_VERSION -- the change only adds. */
+int vrt_physics_run_batch_contacts(vrt_body* d_bodies, int32_t n_runs, int32_t n_bodies, const uint8_t* d_models, int64_t models_bytes,
+                                   const uint8_t* d_remap, int32_t remap_bytes, const double* d_matphys, int32_t n_materials,
+                                   const vrt_physics_params* params, const vrt_physics_run_params* run, int32_t* d_ticks_done,
+                                   vrt_body_sample* d_trace, uint64_t* d_stats, void* stream, uint32_t* d_rng, uint64_t* d_tick_draws,
+                                   const vrt_contact_log* log);
+
 /* Window.chunk_update's selection loop (init.py:447-452) on the device: which world chunks the camera renders this
  * frame and at which LOD.  The voxel blocks stay resident at full resolution; a chunk's LOD is only the resolution
  * byte of its table entry (a Frame of resolution r holds the voxels at coordinates divisible by r, which is what the

@@ -37,9 +37,11 @@ CHUNK_LISTS_UNITS = [os.path.join(HERE, "csrc", "vrt_chunk_lists.hip")]
 PHYSICS_BATCH_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_batch.hip")]
 # ... and those runs with the reference's random draws, a generator per run (vrt_physics_run_batch_draws): a tenth, likewise
 PHYSICS_BATCH_DRAWS_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_batch_draws.hip")]
+# ... and the batch that keeps a contact log per run (vrt_physics_run_batch_contacts): an eleventh, with its own helper header
+PHYSICS_CONTACTS_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_contacts.hip")]
 SOURCES = UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + PHYSICS_RUN_UNITS + PHYSICS_ANIM_UNITS + PHYSICS_RUN_DRAWS_UNITS + CHUNK_LISTS_UNITS + \
-    PHYSICS_BATCH_UNITS + PHYSICS_BATCH_DRAWS_UNITS + \
-    [os.path.join(HERE, "csrc", f) for f in ("vrt_math.h", "vrt_math_consts.h", "vrt_physics_common.h")]
+    PHYSICS_BATCH_UNITS + PHYSICS_BATCH_DRAWS_UNITS + PHYSICS_CONTACTS_UNITS + \
+    [os.path.join(HERE, "csrc", f) for f in ("vrt_math.h", "vrt_math_consts.h", "vrt_physics_common.h", "vrt_physics_contacts.h")]
 SOURCES.append(os.path.join(ROOT, "include", "vrt.h"))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared"] + \
@@ -82,7 +84,8 @@ def build(force=False, verbose=False):
     if not force and not needs_build():
         return SO_PATH
     cmd = [HIPCC] + HIPCC_FLAGS + UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + PHYSICS_RUN_UNITS + PHYSICS_ANIM_UNITS + \
-        PHYSICS_RUN_DRAWS_UNITS + CHUNK_LISTS_UNITS + PHYSICS_BATCH_UNITS + PHYSICS_BATCH_DRAWS_UNITS + ["-o", SO_PATH]
+        PHYSICS_RUN_DRAWS_UNITS + CHUNK_LISTS_UNITS + PHYSICS_BATCH_UNITS + PHYSICS_BATCH_DRAWS_UNITS + \
+        PHYSICS_CONTACTS_UNITS + ["-o", SO_PATH]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -251,6 +254,23 @@ PHYSICS_RUN_DRAWS_BUDGET = 1 << 12   # VRT_PHYSICS_RUN_DRAWS_BUDGET: about 15 ms
 PHYSICS_BATCH_MAX_RUNS, S_PHYSICS_BATCH_BADTICK = 4096, 4
 
 
+class VrtContact(C.Structure):
+    """vrt_contact (include/vrt.h): one record of a run's contact log, 40 bytes."""
+    _fields_ = [("tick", C.c_int32), ("mover", C.c_int32), ("other", C.c_int32), ("step", C.c_int32), ("voxel", C.c_int32 * 3),
+                ("dir", C.c_int8 * 3), ("mat_other", C.c_uint8), ("mat_mover", C.c_uint8), ("reserved", C.c_uint8 * 7)]
+
+
+class VrtContactLog(C.Structure):
+    """vrt_contact_log (include/vrt.h): the records, counts and mask of vrt_physics_run_batch_contacts, 32 bytes."""
+    _fields_ = [("d_records", C.c_void_p), ("d_counts", C.c_void_p), ("d_mask", C.c_void_p), ("capacity", C.c_int32), ("mode", C.c_int32)]
+
+
+CONTACT_FIELDS = [("tick", "<i4"), ("mover", "<i4"), ("other", "<i4"), ("step", "<i4"), ("voxel", "<i4", 3), ("dir", "i1", 3),
+                  ("mat_other", "u1"), ("mat_mover", "u1"), ("reserved", "u1", 7)]
+CONTACT_BYTES = 40
+CONTACTS_VOXELS, CONTACTS_PAIRS = 0, 1   # vrt_contact_log.mode
+CONTACT_MASK_MOVER, CONTACT_MASK_OTHER = 1, 2   # bits of a d_mask byte
+
 
 class VrtAnimSprite(C.Structure):
     """vrt_anim_sprite (include/vrt.h): one animated sprite of vrt_physics_run_anim, 16 bytes."""
@@ -397,6 +417,8 @@ def lib():
                                         vp, vp, vp, vp]
     L.vrt_physics_run_batch_draws.restype = C.c_int
     L.vrt_physics_run_batch_draws.argtypes = L.vrt_physics_run_batch.argtypes + [vp, vp]
+    L.vrt_physics_run_batch_contacts.restype = C.c_int
+    L.vrt_physics_run_batch_contacts.argtypes = L.vrt_physics_run_batch_draws.argtypes + [C.POINTER(VrtContactLog)]
     L.vrt_canvas_blit.restype = C.c_int
     L.vrt_canvas_blit.argtypes = [vp, vp, i32, i32, vp, i64, vp]
     L.vrt_profile_begin.restype = C.c_int
@@ -433,6 +455,7 @@ EXPORTS = ["vrt_abi_version", "vrt_status_string", "vrt_last_hip_error", "vrt_de
            "vrt_synth_volume", "vrt_profile_begin", "vrt_profile_begin_kinds", "vrt_profile_end", "vrt_select_chunks", "vrt_voxelize",
            "vrt_hit_owners", "vrt_chunk_lists_build", "vrt_voxelize_lists", "vrt_hit_owners_lists", "vrt_hit_surfaces", "vrt_edit_models", "vrt_stamp_model", "vrt_physics_tick",
            "vrt_physics_tick_draws", "vrt_physics_run", "vrt_physics_run_batch", "vrt_physics_run_batch_draws",
+           "vrt_physics_run_batch_contacts",
            "vrt_physics_run_draws", "vrt_physics_run_anim"]
 
 

@@ -328,6 +328,60 @@ class PhysicsResult(_LazyStats):
         return int(self.stats[nat.S_PHYSICS_DRAWS])
 
 
+class ContactRecords:
+    """The contact log of one run (world.Contacts is the request): `records`, a numpy structured array of
+    _native.CONTACT_FIELDS with the byte layout of vrt_contact (include/vrt.h) -- tick, mover, other, step, voxel (the world
+    voxel of `other` that was met; the mover's is voxel - dir), dir, mat_other, mat_mover -- in the reference's order, at most
+    `capacity` rows.  `total`: all records the filters passed; `lost`: max(0, total - capacity), those that were counted and not
+    stored.  `materials`: the list `mat_other` and `mat_mover` index; entry 0 is None.  Host and device number the materials
+    alike for a DeviceWorld that meets the sprites for the first time; otherwise compare through `materials`."""
+
+    def __init__(self, records, total, capacity, materials, objects=None):
+        self.records, self.total, self.capacity = records, int(total), int(capacity)
+        self.lost = max(0, self.total - self.capacity)
+        self.materials = list(materials)
+        self._objects = list(objects) if objects is not None else None
+
+    def __len__(self):
+        return len(self.records)
+
+    def _index(self, who):
+        if isinstance(who, (int, np.integer)):
+            return int(who)
+        where = [k for k, o in enumerate(self._objects or ()) if o is who]
+        if not where:
+            raise ValueError("ContactRecords: not an index and not one of the run's objects: %r" % (who,))
+        return where[0]
+
+    def of(self, mover=None, other=None):
+        """The rows whose mover and whose other are the given ones (an Object of the run or an index; None: any)."""
+        keep = np.ones(len(self.records), bool)
+        if mover is not None:
+            keep &= self.records["mover"] == self._index(mover)
+        if other is not None:
+            keep &= self.records["other"] == self._index(other)
+        return self.records[keep]
+
+    def first(self, mover, other=None):
+        """The earliest such row, or None."""
+        rows = self.of(mover, other)
+        return rows[0] if len(rows) else None
+
+    def pairs(self):
+        """One row per (tick, mover, step, other): the first record of each, with `count`, the stored records it stands for --
+        what turns a "voxels" log into touches with their sizes.  A structured array of CONTACT_FIELDS + count."""
+        out = np.zeros(len(self.records), np.dtype(nat.CONTACT_FIELDS + [("count", "<i8")]))
+        n, last = 0, None
+        for r in self.records:
+            key = (int(r["tick"]), int(r["mover"]), int(r["step"]), int(r["other"]))
+            if key != last:
+                for name, *_ in nat.CONTACT_FIELDS:
+                    out[n][name] = r[name]
+                n, last = n + 1, key
+            out[n - 1]["count"] += 1
+        return out[:n]
+
+
 class RunResult(_LazyStats):
     """What DeviceWorld.run() did.  `records`: the body records after the last tick, a numpy structured array of vrt_body
     (include/vrt.h), one per object; their `out` fields are the last tick's (`counters`, as PhysicsResult's), and pad[0] says
@@ -345,10 +399,11 @@ class RunResult(_LazyStats):
     tick, its sprite's frame (-1: not animated) and whether the body made the switch at that tick.
     With rng= (the reference's random draws made on the device): `draws`: the random.random() calls of the run, an int (None
     without rng); `draws_per_tick`: a numpy uint64 array [ticks_run], each tick's (None without rng); word 15 of `stats` is
-    the total as well."""
+    the total as well.
+    With contacts= (the contact log): `contacts`: the run's ContactRecords (None without contacts=)."""
 
     def __init__(self, records, moved, stats_dev, ticks_run, launches, trace_dev, trace_shape, kernel_ms=None, frames=None,
-                 anim_dev=None, draws_per_tick=None):
+                 anim_dev=None, draws_per_tick=None, contacts=None):
         from .world import PHYSICS_COUNTER_FIELDS
         self.records, self.moved, self.kernel_ms = records, moved, kernel_ms
         self.ticks_run, self.launches = ticks_run, launches
@@ -360,6 +415,7 @@ class RunResult(_LazyStats):
         self.frames, self._anim_dev, self._anim = frames, anim_dev, None
         self.draws_per_tick = draws_per_tick
         self.draws = int(draws_per_tick.sum()) if draws_per_tick is not None else None
+        self.contacts = contacts
 
     @property
     def anim(self):
@@ -391,10 +447,13 @@ class BatchRunResult(_LazyStats):
     With rng= (the reference's random draws made on the device, a generator per variant): `draws`: numpy uint64 [K], the
     random.random() calls of each variant (word 15 of its `stats` as well); `draws_per_tick`: numpy uint64 [K][ticks];
     rng_state(k): the state variant k's generator ends in; apply(k, objects, rng=g) also sets g to it.  `draws` and
-    `draws_per_tick` are None for a batch without rng=, and so is what rng_state(k) returns."""
+    `draws_per_tick` are None for a batch without rng=, and so is what rng_state(k) returns.
+    With contacts= (a contact log per variant): contacts(k): variant k's ContactRecords; `contacts_total`: numpy uint64 [K],
+    the records each variant's filters passed; `contacts_lost`: numpy uint64 [K], those beyond the capacity, counted and not
+    stored.  All three are None for a batch without contacts=."""
 
     def __init__(self, records, start, changes, stats_dev, ticks_run, launches, trace_dev, trace_shape, kernel_ms=None,
-                 draws_per_tick=None, rng_words=None, rng_start=None):
+                 draws_per_tick=None, rng_words=None, rng_start=None, contact_log=None):
         from .world import PHYSICS_COUNTER_FIELDS
         self.records, self.kernel_ms = records, kernel_ms
         self.ticks_run, self.launches = ticks_run, launches
@@ -407,6 +466,20 @@ class BatchRunResult(_LazyStats):
         self.draws_per_tick = draws_per_tick
         self.draws = draws_per_tick.sum(axis=1, dtype=np.uint64) if draws_per_tick is not None else None
         self._rng_words, self._rng_start = rng_words, rng_start
+        # (contact_log: the [K][capacity] records as read back, the K counts, the capacity, the materials and the objects)
+        self._contact_log = contact_log
+        self.contacts_total = self.contacts_lost = None
+        if contact_log is not None:
+            self.contacts_total = contact_log[1]
+            self.contacts_lost = np.maximum(contact_log[1], np.uint64(contact_log[2])) - np.uint64(contact_log[2])
+
+    def contacts(self, k):
+        """Variant k's contact log, as run(contacts=) on its twin returns it.  None for a batch without contacts=."""
+        if self._contact_log is None:
+            return None
+        rows, counts, capacity, materials, objects = self._contact_log
+        total = int(counts[k])
+        return ContactRecords(rows[k][:min(total, capacity)].copy(), total, capacity, materials, objects)
 
     def rng_state(self, k):
         """The state variant k's generator ends in, as run(rng=) would have left it: the tuple random.Random.setstate takes,
