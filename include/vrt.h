@@ -1105,6 +1105,62 @@ int vrt_physics_run_batch_contacts(vrt_body* d_bodies, int32_t n_runs, int32_t n
                                    vrt_body_sample* d_trace, uint64_t* d_stats, void* stream, uint32_t* d_rng, uint64_t* d_tick_draws,
                                    const vrt_contact_log* log);
 
+/* SCRIPTED ACCELERATIONS of a batch of runs: Object.accelerate(vel) (data.py:491-492) executed between two ticks of a run, as
+ * the reference's window does for its player after every object's update and mods do for jumps, thrusters, wind and kicks.  An
+ * impulse (tick, body, vel) is `vel = vel + impulse` per component in binary64, done BEFORE tick `tick` begins: after every
+ * body's turn of tick - 1 and before tick `tick` computes its camera, flags and validation; tick 0's come before the first tick.
+ * It is unconditional: a sleeping, invisible or non-physical body, or one without a sprite, takes the velocity and keeps it
+ * until something uses it up.  Several impulses on one body before one tick add in list order (the sum is not associative);
+ * impulses on different bodies commute.  No rule of validation is added: a sum that leaves the limits (|vel| > 1024, not
+ * finite) is refused by the tick's own check, from that tick on, in that run. */
+typedef struct vrt_impulse {     /* 32 bytes */
+    int32_t tick;                /* absolute tick of the run, in [0, n_ticks) */
+    int32_t body;                /* index of the body, in [0, n_bodies) */
+    double  vel[3];              /* what is added to its velocity */
+} vrt_impulse;
+typedef struct vrt_impulse_list {
+    const vrt_impulse* d_impulses;  /* run r's are [d_first[r], d_first[r + 1]), 8-byte aligned; NULL iff none */
+    const int32_t*     d_first;     /* [n_runs + 1], non-decreasing from 0 */
+    int32_t            total;       /* d_first[n_runs] as the host knows it, <= VRT_PHYSICS_MAX_IMPULSES */
+} vrt_impulse_list;
+#define VRT_PHYSICS_MAX_IMPULSES (1 << 20)
+enum { VRT_S_PHYSICS_IMPULSES = 0,     /* entries applied by this launch's share of the run (vrt_physics_run_batch_impulses only) */
+       VRT_S_PHYSICS_IMPULSES_BAD = 1  /* entries skipped, and a bad row of d_first once (likewise) */ };
+
+/* vrt_physics_run_batch_contacts with a list of impulses per run: its arguments in its order, with their meaning -- but `log`
+ * may be NULL: no contact log, and none of its code runs -- then
+ *   impulses      the list, read before the call returns; its arrays are device memory that stays with the caller and that no
+ *                 launch writes.  The host is expected to sort a run's entries by tick, within a tick by body, and to keep the
+ *                 call order of one body's entries at one tick (a stable sort).
+ * The arrays are DEVICE DATA and the kernel trusts none of it.  Entry i of a run belongs to the largest tick in [0, n_ticks)
+ * found among entries 0..i of that run (tick 0 if there is none), so every entry belongs to one tick, whatever it holds.  An
+ * entry is APPLIED at the beginning of the tick it belongs to iff its tick is that tick (so: in range, and not lower than any
+ * in-range tick before it), its body is in [0, n_bodies) and not lower than the body of an earlier entry of that tick that
+ * passed these tests, and its three components are finite.  Every other entry is never applied and is counted in
+ * VRT_S_PHYSICS_IMPULSES_BAD when its tick begins; applied ones are counted in VRT_S_PHYSICS_IMPULSES.  A row of d_first that
+ * decreases, is negative or passes `total` empties that run's list and counts once in VRT_S_PHYSICS_IMPULSES_BAD, in the
+ * launch that starts the run at tick 0.  Nothing outside [0, total) is read, and the kernel terminates on any input.
+ * CHAINING: ticks are absolute.  A launch that starts run r at d_ticks_done[r] = s applies exactly the entries of the ticks >= s
+ * that it reaches; a launch that stopped at the boundary before tick s has not applied tick s's entries.  The next launch
+ * finds its place from s and the list alone -- the first entry whose tick lies in [s, n_ticks) -- and no cursor is kept in
+ * memory.  Both counts are per run and per launch like the other words: their sums over a chain are those of one launch.
+ * WORK grows by one unit per 1024 entries taken in a tick and by nothing in a tick without entries: a run with an empty list
+ * stops at the tick boundaries of vrt_physics_run_batch_contacts (without a log: of vrt_physics_run_batch or
+ * vrt_physics_run_batch_draws), reports its words and leaves its bytes.  A run that is left alone (see there) and n_bodies == 0
+ * look at no entry and count none.
+ * ONE launch of n_runs workgroups of 1024 threads that never communicate; the lane whose entry is the first of its body among
+ * the 1024 taken together adds it and goes on alone through the following entries of that body, so equal bodies add in order
+ * and different bodies in parallel, with plain vector stores and no atomics.
+ * VRT_ERR_ARG, before any HIP call: whatever vrt_physics_run_batch_contacts refuses, but for a NULL log; a NULL `impulses`, a
+ * NULL or misaligned (4 bytes) d_first, total < 0 or > VRT_PHYSICS_MAX_IMPULSES, d_impulses NULL with total > 0 or misaligned
+ * (8 bytes).  Nothing is allocated or synchronised.  A translation unit of its own (vrt_physics_impulses.hip): the other
+ * physics kernels are unchanged, and so is VRT_ABI_VERSION -- the change only adds. */
+int vrt_physics_run_batch_impulses(vrt_body* d_bodies, int32_t n_runs, int32_t n_bodies, const uint8_t* d_models, int64_t models_bytes,
+                                   const uint8_t* d_remap, int32_t remap_bytes, const double* d_matphys, int32_t n_materials,
+                                   const vrt_physics_params* params, const vrt_physics_run_params* run, int32_t* d_ticks_done,
+                                   vrt_body_sample* d_trace, uint64_t* d_stats, void* stream, uint32_t* d_rng, uint64_t* d_tick_draws,
+                                   const vrt_contact_log* log, const vrt_impulse_list* impulses);
+
 /* Window.chunk_update's selection loop (init.py:447-452) on the device: which world chunks the camera renders this
  * frame and at which LOD.  The voxel blocks stay resident at full resolution; a chunk's LOD is only the resolution
  * byte of its table entry (a Frame of resolution r holds the voxels at coordinates divisible by r, which is what the

@@ -39,8 +39,10 @@ PHYSICS_BATCH_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_batch.hip")]
 PHYSICS_BATCH_DRAWS_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_batch_draws.hip")]
 # ... and the batch that keeps a contact log per run (vrt_physics_run_batch_contacts): an eleventh, with its own helper header
 PHYSICS_CONTACTS_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_contacts.hip")]
+# ... and the batch that takes scripted accelerations per run, with or without a log (vrt_physics_run_batch_impulses): a twelfth
+PHYSICS_IMPULSES_UNITS = [os.path.join(HERE, "csrc", "vrt_physics_impulses.hip")]
 SOURCES = UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + PHYSICS_RUN_UNITS + PHYSICS_ANIM_UNITS + PHYSICS_RUN_DRAWS_UNITS + CHUNK_LISTS_UNITS + \
-    PHYSICS_BATCH_UNITS + PHYSICS_BATCH_DRAWS_UNITS + PHYSICS_CONTACTS_UNITS + \
+    PHYSICS_BATCH_UNITS + PHYSICS_BATCH_DRAWS_UNITS + PHYSICS_CONTACTS_UNITS + PHYSICS_IMPULSES_UNITS + \
     [os.path.join(HERE, "csrc", f) for f in ("vrt_math.h", "vrt_math_consts.h", "vrt_physics_common.h", "vrt_physics_contacts.h")]
 SOURCES.append(os.path.join(ROOT, "include", "vrt.h"))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -85,7 +87,7 @@ def build(force=False, verbose=False):
         return SO_PATH
     cmd = [HIPCC] + HIPCC_FLAGS + UNITS + PHYSICS_UNITS + PHYSICS_DRAWS_UNITS + PHYSICS_RUN_UNITS + PHYSICS_ANIM_UNITS + \
         PHYSICS_RUN_DRAWS_UNITS + CHUNK_LISTS_UNITS + PHYSICS_BATCH_UNITS + PHYSICS_BATCH_DRAWS_UNITS + \
-        PHYSICS_CONTACTS_UNITS + ["-o", SO_PATH]
+        PHYSICS_CONTACTS_UNITS + PHYSICS_IMPULSES_UNITS + ["-o", SO_PATH]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -272,6 +274,22 @@ CONTACTS_VOXELS, CONTACTS_PAIRS = 0, 1   # vrt_contact_log.mode
 CONTACT_MASK_MOVER, CONTACT_MASK_OTHER = 1, 2   # bits of a d_mask byte
 
 
+class VrtImpulse(C.Structure):
+    """vrt_impulse (include/vrt.h): Object.accelerate(vel) on `body` before tick `tick` of a run, 32 bytes."""
+    _fields_ = [("tick", C.c_int32), ("body", C.c_int32), ("vel", C.c_double * 3)]
+
+
+class VrtImpulseList(C.Structure):
+    """vrt_impulse_list (include/vrt.h): all runs' entries and the rows' bounds of vrt_physics_run_batch_impulses, 24 bytes."""
+    _fields_ = [("d_impulses", C.c_void_p), ("d_first", C.c_void_p), ("total", C.c_int32)]
+
+
+IMPULSE_FIELDS = [("tick", "<i4"), ("body", "<i4"), ("vel", "<f8", 3)]
+IMPULSE_BYTES = 32
+PHYSICS_MAX_IMPULSES = 1 << 20   # VRT_PHYSICS_MAX_IMPULSES
+S_PHYSICS_IMPULSES, S_PHYSICS_IMPULSES_BAD = 0, 1   # entries applied, entries skipped (vrt_physics_run_batch_impulses only)
+
+
 class VrtAnimSprite(C.Structure):
     """vrt_anim_sprite (include/vrt.h): one animated sprite of vrt_physics_run_anim, 16 bytes."""
     _fields_ = [("frame", C.c_int32), ("n_frames", C.c_int32), ("first_row", C.c_int32), ("pad", C.c_int32)]
@@ -419,6 +437,8 @@ def lib():
     L.vrt_physics_run_batch_draws.argtypes = L.vrt_physics_run_batch.argtypes + [vp, vp]
     L.vrt_physics_run_batch_contacts.restype = C.c_int
     L.vrt_physics_run_batch_contacts.argtypes = L.vrt_physics_run_batch_draws.argtypes + [C.POINTER(VrtContactLog)]
+    L.vrt_physics_run_batch_impulses.restype = C.c_int
+    L.vrt_physics_run_batch_impulses.argtypes = L.vrt_physics_run_batch_contacts.argtypes + [C.POINTER(VrtImpulseList)]
     L.vrt_canvas_blit.restype = C.c_int
     L.vrt_canvas_blit.argtypes = [vp, vp, i32, i32, vp, i64, vp]
     L.vrt_profile_begin.restype = C.c_int
@@ -455,7 +475,7 @@ EXPORTS = ["vrt_abi_version", "vrt_status_string", "vrt_last_hip_error", "vrt_de
            "vrt_synth_volume", "vrt_profile_begin", "vrt_profile_begin_kinds", "vrt_profile_end", "vrt_select_chunks", "vrt_voxelize",
            "vrt_hit_owners", "vrt_chunk_lists_build", "vrt_voxelize_lists", "vrt_hit_owners_lists", "vrt_hit_surfaces", "vrt_edit_models", "vrt_stamp_model", "vrt_physics_tick",
            "vrt_physics_tick_draws", "vrt_physics_run", "vrt_physics_run_batch", "vrt_physics_run_batch_draws",
-           "vrt_physics_run_batch_contacts",
+           "vrt_physics_run_batch_contacts", "vrt_physics_run_batch_impulses",
            "vrt_physics_run_draws", "vrt_physics_run_anim"]
 
 

@@ -400,10 +400,12 @@ class RunResult(_LazyStats):
     With rng= (the reference's random draws made on the device): `draws`: the random.random() calls of the run, an int (None
     without rng); `draws_per_tick`: a numpy uint64 array [ticks_run], each tick's (None without rng); word 15 of `stats` is
     the total as well.
-    With contacts= (the contact log): `contacts`: the run's ContactRecords (None without contacts=)."""
+    With contacts= (the contact log): `contacts`: the run's ContactRecords (None without contacts=).
+    With impulses= (scripted accelerations): `impulses_applied`, `impulses_skipped`: the entries the device added to a
+    velocity and those it refused to, ints (None without impulses=); words 0 and 1 of `stats` as well."""
 
     def __init__(self, records, moved, stats_dev, ticks_run, launches, trace_dev, trace_shape, kernel_ms=None, frames=None,
-                 anim_dev=None, draws_per_tick=None, contacts=None):
+                 anim_dev=None, draws_per_tick=None, contacts=None, impulses=False):
         from .world import PHYSICS_COUNTER_FIELDS
         self.records, self.moved, self.kernel_ms = records, moved, kernel_ms
         self.ticks_run, self.launches = ticks_run, launches
@@ -416,6 +418,15 @@ class RunResult(_LazyStats):
         self.draws_per_tick = draws_per_tick
         self.draws = int(draws_per_tick.sum()) if draws_per_tick is not None else None
         self.contacts = contacts
+        self._impulses = bool(impulses)
+
+    @property
+    def impulses_applied(self):
+        return int(self.stats[nat.S_PHYSICS_IMPULSES]) if self._impulses else None
+
+    @property
+    def impulses_skipped(self):
+        return int(self.stats[nat.S_PHYSICS_IMPULSES_BAD]) if self._impulses else None
 
     @property
     def anim(self):
@@ -450,10 +461,13 @@ class BatchRunResult(_LazyStats):
     `draws_per_tick` are None for a batch without rng=, and so is what rng_state(k) returns.
     With contacts= (a contact log per variant): contacts(k): variant k's ContactRecords; `contacts_total`: numpy uint64 [K],
     the records each variant's filters passed; `contacts_lost`: numpy uint64 [K], those beyond the capacity, counted and not
-    stored.  All three are None for a batch without contacts=."""
+    stored.  All three are None for a batch without contacts=.
+    With impulses= or the "impulses" key of a variant (scripted accelerations): `impulses_applied`, `impulses_skipped`: numpy
+    uint64 [K], the entries each variant added to a velocity and those the device refused to (words 0 and 1 of its `stats`);
+    None for a batch without impulses.  The final records hold what the impulses did: apply(k, objects) needs nothing more."""
 
     def __init__(self, records, start, changes, stats_dev, ticks_run, launches, trace_dev, trace_shape, kernel_ms=None,
-                 draws_per_tick=None, rng_words=None, rng_start=None, contact_log=None):
+                 draws_per_tick=None, rng_words=None, rng_start=None, contact_log=None, impulses=False):
         from .world import PHYSICS_COUNTER_FIELDS
         self.records, self.kernel_ms = records, kernel_ms
         self.ticks_run, self.launches = ticks_run, launches
@@ -468,10 +482,19 @@ class BatchRunResult(_LazyStats):
         self._rng_words, self._rng_start = rng_words, rng_start
         # (contact_log: the [K][capacity] records as read back, the K counts, the capacity, the materials and the objects)
         self._contact_log = contact_log
+        self._impulses = bool(impulses)
         self.contacts_total = self.contacts_lost = None
         if contact_log is not None:
             self.contacts_total = contact_log[1]
             self.contacts_lost = np.maximum(contact_log[1], np.uint64(contact_log[2])) - np.uint64(contact_log[2])
+
+    @property
+    def impulses_applied(self):
+        return self.stats[:, nat.S_PHYSICS_IMPULSES].astype(np.uint64) if self._impulses else None
+
+    @property
+    def impulses_skipped(self):
+        return self.stats[:, nat.S_PHYSICS_IMPULSES_BAD].astype(np.uint64) if self._impulses else None
 
     def contacts(self, k):
         """Variant k's contact log, as run(contacts=) on its twin returns it.  None for a batch without contacts=."""

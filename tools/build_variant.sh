@@ -10,6 +10,6 @@ name=$1; shift
     python_raytracer_amd/csrc/vrt_physics_run.hip python_raytracer_amd/csrc/vrt_physics_anim.hip \
     python_raytracer_amd/csrc/vrt_physics_run_draws.hip python_raytracer_amd/csrc/vrt_chunk_lists.hip \
     python_raytracer_amd/csrc/vrt_physics_batch.hip python_raytracer_amd/csrc/vrt_physics_batch_draws.hip \
-    python_raytracer_amd/csrc/vrt_physics_contacts.hip \
+    python_raytracer_amd/csrc/vrt_physics_contacts.hip python_raytracer_amd/csrc/vrt_physics_impulses.hip \
     -o python_raytracer_amd/_vrt_${name}.so
 echo python_raytracer_amd/_vrt_${name}.so
